@@ -13,12 +13,16 @@ N > 1 GPUs: GPT-J-6B is below the >=12B threshold at which the north star splits
 so each rank decodes its own stream (replicas, weak scaling, no collective on the data
 path); value = all ranks' tokens / max-over-ranks time.  `--config gpt-neoxt-20b
 --pipeline` runs the 20B layer split with one RCCL send of the residual per stage; the
-default run also measures that split over the same N ranks in a child job and reports it
+`--full` run also measures that split over the same N ranks in a child job and reports it
 beside the headline as `pipeline_20b` (north star: 1/2/4/8-GPU numbers for the 20B).
 
-Prints ONE JSON line (rank 0) with `roofline` (the Q4_0 GEMV kernel: algorithmic weight
-bytes / event-timed average launch) and `cpu_baseline` (the CPU oracle on the host cores: the
-full 28-layer model, decode tokens timed at the job's threads and at 1 thread).
+Prints ONE JSON line (rank 0).  A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms
+up, times the N steps and prints the headline figure.  `--full` adds everything else the
+line can hold, each under its own `--no-*` switch: `roofline` (the Q4_0 GEMV kernel:
+algorithmic weight bytes / event-timed average launch, a second pass of the same steps),
+`fast_mode`, `cpu_baseline` (the CPU oracle on the host cores: the full 28-layer model, decode
+tokens timed at the job's threads and at 1 thread), `other_configs`, `prefill_codegen16b` and
+`pipeline_20b`.  `--dump-outputs DIR` writes what the last timed step computed (below).
 """
 from __future__ import annotations
 
@@ -194,6 +198,33 @@ def q4_weight_bytes(arch: str, hp: mg.HParams) -> float:
     """B_w per decode token: every Q4_0 matrix incl. lm_head, 0.625 B/w."""
     E, F, L, V = hp.n_embd, hp.n_ff, hp.n_layer, hp.n_vocab
     return 0.625 * (L * (4 * E * E + 2 * E * F) + V * E)
+
+
+def device_logits(model) -> np.ndarray:
+    """The logits row the model's last eval left on the device (vsim_model_logits_dev), copied to
+    the host with the HIP runtime libvsim_hip.so itself is linked to.  The model's stream is idle
+    (eval / generate return after their own copies)."""
+    import ctypes
+    L = hip.lib()
+    L.hipMemcpy.restype = ctypes.c_int
+    L.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    out = np.zeros(model.n_vocab, np.float32)
+    src = L.vsim_model_logits_dev(model.h)
+    if not src:
+        raise hip.VsimError("the model has no logits buffer")
+    rc = L.hipMemcpy(out.ctypes.data, src, out.nbytes, 2)  # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise hip.VsimError(f"hipMemcpy of the logits failed ({rc})")
+    return out
+
+
+def dump_outputs(path: str, **arrays) -> None:
+    """--dump-outputs: what the timed path handed its caller in its last step, one
+    DIR/<name>.npy each (float32 / float64; a few hundred KB at the largest vocabulary)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(path, f"{name}.npy"), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def host_cpu():
@@ -408,6 +439,12 @@ def run_pipeline(args, world, rank, dev, dist):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # the greedy token of the last step, back on rank 0; a single stage also holds its logits
+        out = {"tokens": tok_dev.cpu().numpy()}
+        if last:
+            out["logits"] = device_logits(model)
+        dump_outputs(args.dump_outputs, **out)
     value = args.steps / elapsed
     bw = q4_weight_bytes(arch_s, hp)
     line = {
@@ -527,9 +564,11 @@ def run_prefill(args, dev):
     reps = max(1, args.steps)
     t0 = time.perf_counter()
     for _ in range(reps):
-        model.eval(0, ids)
+        logits = model.eval(0, ids)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / reps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits=logits)  # the last timed prompt's last row
     exact = None
     if args.prefill_exact:
         model.set_mode(hip.MODE_EXACT)
@@ -551,7 +590,7 @@ def run_prefill(args, dev):
     print(json.dumps({
         "metric": f"prefill tokens/s {args.config} Q4_0 seq={N} @1 GPU (fp16 MFMA dequant-GEMM)",
         "value": round(N / dt, 1), "unit": "tokens/s", "n_gpus": 1, "steps": reps,
-        "ms_per_prompt": round(dt * 1e3, 2), "higher_is_better": True,
+        "ms_per_prompt": round(dt * 1e3, 2), "ms_per_step": round(dt * 1e3, 4), "higher_is_better": True,
         "first_prompt_ms": round(first * 1e3, 2), "reserve_ms": round(reserve * 1e3, 2),
         "weight_images_GB": 0.0,  # (r03: the GEMM dequantizes the Q4_0 weights in LDS, no fp16 copies)
         "dtype": "f16 MFMA, f32 accumulate", "data": "synthetic (random-init weights, drawn on device)",
@@ -572,6 +611,11 @@ def main():
                                                               "codegen-16B"])
     ap.add_argument("--mode", default="exact", choices=["exact", "fast"])
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline pass, the fast-mode, CPU, pythia-12b, codegen-16B "
+                         "prefill and 20B pipeline companions (each has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (tokens, logits) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-fast", action="store_true", help="skip the fast-mode companion measurement")
@@ -590,6 +634,11 @@ def main():
     ap.add_argument("--no-prefill-companion", action="store_true",
                     help="skip the bounded codegen-16B 2048-token prefill companion measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_profile = args.no_fast = args.no_cpu_baseline = True
+        args.no_other_configs = args.no_prefill_companion = args.no_pipeline_20b = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -631,9 +680,12 @@ def main():
         # the next without a host round trip; the same tokens as eval() + numpy.argmax
         # (tests/test_gpu_model.py::test_generate_matches_stepwise_greedy)
         nonlocal n_past, tok
+        toks = []
         if k:
-            tok = model.generate(n_past, tok, k)[-1]
+            toks = model.generate(n_past, tok, k)
+            tok = toks[-1]
             n_past += k
+        return toks
 
     run_steps(args.warmup)
     start = (n_past, tok)  # the profile pass and the fast companion replay these positions
@@ -646,13 +698,17 @@ def main():
 
     barrier()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    timed_tokens = run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what generate() handed back (the timed steps' greedy tokens) and the logits row its last
+        # step left on the device, before any later pass evaluates again
+        dump_outputs(args.dump_outputs, tokens=np.asarray(timed_tokens, np.float64), logits=device_logits(model))
 
     # live roofline of the dominant kernel: an event pair around every launch (per kernel
     # kind, with its algorithmic bytes), over a second pass of the same decode steps

@@ -15,6 +15,7 @@ Usage:  make -C oracle ref && python tests/golden/make_golden.py
 """
 from __future__ import annotations
 
+import glob
 import hashlib
 import json
 import os
@@ -40,6 +41,28 @@ def tmp(name):
 
 def harness(*args):
     subprocess.run([HARNESS, *[str(a) for a in args]], check=True)
+
+
+def save_split(name, cases, limit=1 << 20):
+    """ops_<name>.npz, and ops_<name>.partN.npz for the cases (cN_*) that would take a file past
+    `limit` bytes (no committed file above 1 MiB); golden_util.ops() merges them."""
+    for old in glob.glob(os.path.join(OUT, f"ops_{name}.part*.npz")):
+        os.remove(old)
+    ids = sorted({k.split("_")[0] for k in cases}, key=lambda c: int(c[1:]))
+    part, cur = 0, {}
+
+    def path():
+        return os.path.join(OUT, f"ops_{name}.npz" if part == 0 else f"ops_{name}.part{part}.npz")
+
+    for c in ids:
+        add = {k: v for k, v in cases.items() if k.startswith(c + "_")}
+        np.savez_compressed(path(), **cur, **add)
+        if cur and os.path.getsize(path()) > limit:
+            np.savez_compressed(path(), **cur)
+            part, cur = part + 1, {}
+        cur.update(add)
+    np.savez_compressed(path(), **cur)
+    assert os.path.getsize(path()) <= limit, f"{path()}: one case alone exceeds {limit} bytes"
 
 
 def fread(path, dtype):
@@ -84,7 +107,7 @@ def gen_ops():
         cases[f"c{ci}_w"] = w
         cases[f"c{ci}_x"] = xa
         cases[f"c{ci}_y"] = fread(tmp("y"), np.float32)
-    np.savez_compressed(os.path.join(OUT, "ops_mulmat.npz"), **cases)
+    save_split("mulmat", cases)
 
     # LayerNorm
     cases = {}

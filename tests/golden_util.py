@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import functools
+import glob
 import hashlib
 import json
 import os
@@ -14,13 +15,20 @@ from vsim_amd import modelgen as mg
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def ops(name: str):
-    return np.load(os.path.join(GOLDEN, f"ops_{name}.npz"))
+def ops(name: str) -> dict:
+    """The arrays of ops_<name>.npz; a fixture too large for one committed file (1 MiB) continues
+    in ops_<name>.partN.npz (make_golden.py's save_split), whose arrays are merged in."""
+    out = {}
+    parts = sorted(glob.glob(os.path.join(GOLDEN, f"ops_{name}.part*.npz")))
+    for path in [os.path.join(GOLDEN, f"ops_{name}.npz")] + parts:
+        with np.load(path) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def cases(z):
-    ids = sorted({k.split("_")[0] for k in z.files})
-    return [{k.split("_", 1)[1]: z[k] for k in z.files if k.startswith(c + "_")} for c in ids]
+    ids = sorted({k.split("_")[0] for k in z})
+    return [{k.split("_", 1)[1]: z[k] for k in z if k.startswith(c + "_")} for c in ids]
 
 
 @functools.lru_cache(maxsize=None)

@@ -5,6 +5,7 @@ set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 STEPS=${STEPS:-64}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: roofline, companions, CPU baseline
 stop_if_fatal() {  # $1 = exit code, $2 = step name ; test failures (1) are not fatal
   local rc=$1
   echo "[gpu_check] $2 exit=$rc"

@@ -22,11 +22,11 @@ for m in exact fast; do
   f=$(find "$out/pmc_${m}_$tag" -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$root/profiles/${tag}_pmc_fetch_$m.csv" && cp "$f" "$out/${tag}_pmc_fetch_$m.csv"
 done
-timeout -k 10 400 python3 "$root/bench.py" > "$out/bench_default_$tag.log" 2>&1
+timeout -k 10 400 python3 "$root/bench.py" --full > "$out/bench_default_$tag.log" 2>&1
 fatal $? bench; tail -1 "$out/bench_default_$tag.log"
 timeout -k 10 300 python3 "$root/bench.py" --config codegen-16B --prefill 2048 --steps 3 > "$out/bench_prefill_$tag.log" 2>&1
 fatal $? prefill; tail -1 "$out/bench_prefill_$tag.log"
-timeout -k 10 300 python3 "$root/bench.py" --config bloom-560m --steps 128 --no-cpu-baseline > "$out/bench_bloom_$tag.log" 2>&1
+timeout -k 10 300 python3 "$root/bench.py" --full --config bloom-560m --steps 128 --no-cpu-baseline > "$out/bench_bloom_$tag.log" 2>&1
 fatal $? bloom; tail -1 "$out/bench_bloom_$tag.log" | cut -c1-200
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$out/prof_exact_$tag" -o run --output-format csv -- \
   python3 "$root/bench.py" --steps 64 --warmup 4 --no-cpu-baseline --no-pipeline-20b --no-fast --no-profile --no-other-configs --no-prefill-companion > "$out/prof_exact_$tag.log" 2>&1

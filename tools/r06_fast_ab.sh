@@ -23,7 +23,7 @@ done
 for rep in 1 2; do
   for v in $V; do
     lib=""; [ "$v" != product ] && lib=$root/vsim_amd/_build/var/$v.so
-    env VSIM_LIB=$lib timeout -k 10 200 python3 "$root/bench.py" --mode fast --no-cpu-baseline --no-pipeline-20b --no-fast \
+    env VSIM_LIB=$lib timeout -k 10 200 python3 "$root/bench.py" --full --mode fast --no-cpu-baseline --no-pipeline-20b --no-fast \
       --no-other-configs --no-prefill-companion > "$out/r06_${tag}_bench_${v}_${rep}.log" 2>&1
     rc=$?; [ "$rc" -ne 0 ] && { echo "[bench $v] exit=$rc"; tail -5 "$out/r06_${tag}_bench_${v}_${rep}.log"; exit $rc; }
     python3 - "$out/r06_${tag}_bench_${v}_${rep}.log" "$v" <<'PY'

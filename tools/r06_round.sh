@@ -13,7 +13,7 @@ for m in exact fast prefill; do
 done
 cd /tmp && export TMPDIR=/tmp
 for cfg in pythia-12b gpt-neoxt-20b; do
-  timeout -k 10 400 python3 "$root/bench.py" --config $cfg --no-cpu-baseline --no-pipeline-20b --no-fast --no-other-configs \
+  timeout -k 10 400 python3 "$root/bench.py" --full --config $cfg --no-cpu-baseline --no-pipeline-20b --no-fast --no-other-configs \
     --no-prefill-companion > "$out/r06_bench_$cfg.log" 2>&1 || { echo "[r06_round] $cfg exit=$?"; exit 1; }
   tail -1 "$out/r06_bench_$cfg.log" | cut -c1-160
 done

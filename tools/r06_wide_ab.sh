@@ -14,7 +14,7 @@ for rep in 1 2; do
   for c in ${CONFIGS:-pythia-12b gpt-neoxt-20b}; do
     for v in ${VARIANTS:-prev product}; do
       lib=""; [ "$v" != product ] && lib=$root/vsim_amd/_build/var/$v.so
-      env VSIM_LIB=$lib timeout -k 10 300 python3 "$root/bench.py" --config "$c" --steps ${STEPS:-120} --no-cpu-baseline \
+      env VSIM_LIB=$lib timeout -k 10 300 python3 "$root/bench.py" --full --config "$c" --steps ${STEPS:-120} --no-cpu-baseline \
         --no-pipeline-20b --no-fast --no-other-configs --no-prefill-companion > "$out/r06_${tag}_${c}_${v}_${rep}.log" 2>&1
       rc=$?; [ "$rc" -ne 0 ] && { echo "[bench $c $v] exit=$rc"; tail -5 "$out/r06_${tag}_${c}_${v}_${rep}.log"; exit $rc; }
       python3 - "$out/r06_${tag}_${c}_${v}_${rep}.log" "$c $v" <<'PY'

@@ -641,7 +641,14 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm_f16_256(const _Float16 *
   }
 #undef G2_SYNC_MMA
   if (!wr) __builtin_amdgcn_s_barrier();  // (pairs with group 1's last barrier)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped DMAs past the end have landed
+  // the clamped DMAs past the end have landed.  Q4A: so have the clamped raw blocks of tile nk + 1,
+  // which P3's vmcnt(2) left in flight: the wait names their registers, or the compiler, which does
+  // not know of the pending writes, may hand the dead registers to the epilogue's first values
+  // above the wait, where a late load overwrites them
+  if constexpr (Q4A)
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(qraw_n), "+v"(qd_n)::"memory");
+  else
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // C/D map of the 16x16 MFMA: column (token) = lane & 15, rows (weight rows) 4 * (lane >> 4) + reg
   __syncthreads();  // (every wave is past its last LDS operand read)
   g2_epilogue<GQ, EM, BM / 2, g2_lds_bytes(AP)>(acc, m0 + wr * (BM / 2), n0 + wc * 64, M, N, bias, Y, gelu_tab, Q16, epi,
@@ -831,7 +838,12 @@ __global__ void __launch_bounds__(G2_THREADS, 1) k_gemm_q4r(const W4 WQ, int M, 
     }
 #undef R_PHASE
     if (!wr) __builtin_amdgcn_s_barrier();  // (pairs with group 1's last barrier)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the clamped loads past the end have landed
+    // the clamped loads past the end have landed (the wait names the raw registers: the compiler
+    // does not know of the pending writes and could otherwise reuse the dead registers above it)
+    asm volatile("s_waitcnt vmcnt(0)"
+                 : "+v"(rw[0][0]), "+v"(rw[0][1]), "+v"(rw[0][2]), "+v"(rw[0][3]), "+v"(rw[1][0]), "+v"(rw[1][1]),
+                   "+v"(rw[1][2]), "+v"(rw[1][3]), "+v"(rd[0][0]), "+v"(rd[0][1]), "+v"(rd[0][2]), "+v"(rd[0][3]),
+                   "+v"(rd[1][0]), "+v"(rd[1][1]), "+v"(rd[1][2]), "+v"(rd[1][3])::"memory");
     __syncthreads();
   };
   // tile t of the launch order -> its first row and column.  Column groups of sk.cg tile-columns,
