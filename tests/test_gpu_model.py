@@ -232,6 +232,63 @@ def test_kernel_counts_per_graph_kind(tmp_path):
     m.close()
 
 
+@pytest.mark.parametrize("cfg", ["tiny-neox", "tiny-gptj"])
+def test_scratch_regrow_under_captured_graphs(cfg, tmp_path):
+    """A prompt longer than the scratch (sized for 16 tokens) frees and regrows every scratch
+    buffer while all four step graphs (eval, eval_argmax, generate, stage step) are captured on
+    the old addresses: the graphs must go with the buffers and be captured again.  The same four
+    calls before and after the regrow give the CPU oracle's logits bit for bit, the argmax of
+    the oracle's logits as tokens, and the same kernels_per_eval."""
+    import oracle_py as O
+    import torch
+    arch_s, hp = mg.CONFIGS[cfg]
+    arch = hip.ARCH_GPTJ if arch_s == "gptj" else hip.ARCH_GPTNEOX
+    path = str(tmp_path / "regrow.bin")
+    mg.write_model(path, arch_s, hp, seed=7, std=0.05)
+    om = O.Model(path, arch, n_ctx=64)
+    m = hip.Model.load(path, arch, n_ctx=64)
+    m.set_graph(True)
+    tok = torch.zeros(1, dtype=torch.int32, device="cuda")
+    m.stage_bind(tok_in=tok.data_ptr(), tok_out=tok.data_ptr())
+
+    def same_bits(got, want, what):
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), what
+
+    def four_calls(n_past, t, what):
+        """eval, eval_argmax, generate(2), stage_begin + stage_step from n_past; each call's kernel count."""
+        counts = {}
+        lo = om.eval(n_past, [t])
+        same_bits(m.eval(n_past, [t]), lo, f"{what}: eval")
+        counts["eval"] = m.info()["kernels_per_eval"]
+        t = int(np.argmax(lo))
+        want = int(np.argmax(om.eval(n_past + 1, [t])))
+        assert m.eval_argmax(n_past + 1, t) == want, f"{what}: eval_argmax"
+        counts["argmax"] = m.info()["kernels_per_eval"]
+        want2 = [int(np.argmax(om.eval(n_past + 2, [want])))]
+        want2.append(int(np.argmax(om.eval(n_past + 3, [want2[0]]))))
+        assert m.generate(n_past + 2, want, 2) == want2, f"{what}: generate"
+        counts["generate"] = m.info()["kernels_per_eval"]
+        tok.fill_(want2[1])
+        torch.cuda.synchronize()
+        m.stage_begin(n_past + 4)
+        m.stage_step()
+        counts["stage"] = m.info()["kernels_per_eval"]
+        m.sync()
+        assert int(tok.item()) == int(np.argmax(om.eval(n_past + 4, [want2[1]]))), f"{what}: stage_step"
+        return counts
+
+    short = [1, 2, 3]
+    lo = om.eval(0, short)
+    same_bits(m.eval(0, short), lo, "3-token prompt")
+    before = four_calls(len(short), int(np.argmax(lo)), "before the regrow")
+    long = [(7 * i + 3) % hp.n_vocab for i in range(24)]  # > 16 tokens: ensure_scratch regrows
+    lo = om.eval(0, long)
+    same_bits(m.eval(0, long), lo, "24-token prompt")
+    after = four_calls(len(long), int(np.argmax(lo)), "after the regrow")
+    assert after == before, (after, before)
+    m.close()
+
+
 @pytest.mark.parametrize("cfg", ["small-gptj", "small-neox", "small-bloom", "small-neox-serial"])
 def test_graph_replay_bit_exact_vs_oracle(cfg, tmp_path):
     """The decode step captured once in a hipGraph and replayed (n_past and the token read

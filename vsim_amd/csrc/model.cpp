@@ -6,6 +6,12 @@
 // ([layer][n_ctx][E], vsim.cpp:349-366) and all activations stay in HBM; per eval the
 // host sends the token ids and receives one logits row (vsim.cpp:736-737).
 // A pipeline stage owns layers [l0, l1); stages exchange the residual inpL ([N][E] f32).
+//
+// What the host side keeps is described once each: the tensors of an architecture
+// (arch_table: plan_slots and bind_pointers walk it), the scratch buffers (scratch_table:
+// allocated, freed and poisoned from it), the four single-token step graphs (StepGraph
+// step[4], captured by decode_graph) and what a step of each kind enqueues (enqueue_step:
+// the captured and the eager form are the same call).  LAUNCH brackets a profiled launch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,6 +46,21 @@ struct LayerW {
   void *wq = nullptr, *wk = nullptr, *wv = nullptr, *wo = nullptr, *wfc = nullptr, *wproj = nullptr;
   float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
   float *bq = nullptr, *bk = nullptr, *bv = nullptr, *bo = nullptr, *bfc = nullptr, *bproj = nullptr;
+};
+
+// The single-token step, captured once per kind and mode as a hipGraph (decode_graph):
+//   STEP_LOGITS  vsim_model_eval: uploads, the decode kernels, the logits copy-out
+//   STEP_ARGMAX  the greedy variant: device argmax, 4-byte copy-out instead of the logits
+//   STEP_GEN     the device-resident greedy loop (vsim_model_generate): no uploads, no copy-out;
+//                the argmax kernel feeds tok_dev / npast_dev and records into hist_dev[n_ctx]
+//   STEP_STAGE   the pipeline stage step (vsim_model_stage_*) between the bound device buffers,
+//                ending by advancing n_past on the device
+enum StepKind { STEP_LOGITS = 0, STEP_ARGMAX = 1, STEP_GEN = 2, STEP_STAGE = 3 };
+struct StepGraph {
+  hipGraph_t graph = nullptr;
+  hipGraphExec_t exec = nullptr;
+  int mode = -1;    // the mode it was captured in (-1: recapture on next use)
+  int kernels = 0;  // kernels in one replay
 };
 
 }  // namespace
@@ -78,37 +99,23 @@ struct vsim_model {
   float *logit_host = nullptr;  // pinned
   int kernels_last = 0;
 
-  // fused single-token decode step (layer.hip) and its hipGraph
+  // fused single-token decode step (layer.hip) and its graphs
   uint8_t *xqa = nullptr;     // attention output, quantized
   float *xda = nullptr;
   float *inpL2 = nullptr;     // second residual buffer (the join alternates between the two)
   float *resid_final = nullptr;  // where the last fused step left the stage's residual
   int *npast_dev = nullptr, *npast_host = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  // greedy variant of the decode graph: device argmax, 4-byte copy-out instead of the logits
-  hipGraph_t graph_am = nullptr;
-  hipGraphExec_t gexec_am = nullptr;
-  int graph_am_mode = -1;
-  int *am_dev = nullptr, *am_host = nullptr;
+  StepGraph step[4];  // by StepKind
+  int *am_dev = nullptr, *am_host = nullptr;  // the greedy steps' token
   unsigned long long *am_ws = nullptr;  // the argmax's key and workgroup count (zero between launches)
-  // device-resident greedy loop (vsim_model_generate): graph without uploads; the argmax
-  // kernel feeds tok_dev / npast_dev and records into hist_dev[n_ctx]
-  hipGraph_t graph_gen = nullptr;
-  hipGraphExec_t gexec_gen = nullptr;
-  int graph_gen_mode = -1;
-  int *hist_dev = nullptr;
+  int *hist_dev = nullptr;              // STEP_GEN's record [n_ctx]
   // pipeline stage step (vsim_model_stage_*): device buffers the caller binds (the token in
   // on the first stage, the residual in / out between stages, the greedy token out on the
-  // last), a graph of the whole step that ends by advancing n_past on the device, and the
-  // host's count of enqueued steps (n_ctx bound)
+  // last) and the host's count of enqueued steps (n_ctx bound)
   const int32_t *st_tok_in = nullptr;
   const float *st_resid_in = nullptr;
   float *st_resid_out = nullptr;
   int32_t *st_tok_out = nullptr;
-  hipGraph_t graph_st = nullptr;
-  hipGraphExec_t gexec_st = nullptr;
-  int graph_st_mode = -1;
   int st_npast = -1;
   unsigned *tail_done = nullptr;  // the fast decode step's per-head counters (fast_decode.hip)
   // the tail LayerNorm's hand-off buffers (TailLn): the step epoch, the out-projection's and the joined row's
@@ -124,14 +131,12 @@ struct vsim_model {
   void *pf_x16 = nullptr;      // fast prefill: fp16 GEMM operands, [n_max][E] then [n_max][4E]
   size_t pf_bytes = 0;
 
-  int graph_mode = -1;
   // graph executor's fast path (graph.cpp): weights and KV cache borrowed from its device
   // mirrors (not freed here), the KQV key grouping of the caller's thread count and the
   // scale the graph carries (0: computed from the hparams)
   bool borrowed = false;
   int kqv_nth = 1;
   float attn_scale = 0.0f;
-  int graph_kernels_kind[4] = {0, 0, 0, 0};  // per decode_graph kind: kernels in one replay
 
   // Per-kernel profiling (bench.py's live roofline): with profiling on, the decode step runs
   // eagerly and an event pair brackets every launch, tagged with the kernel's name and the
@@ -158,72 +163,88 @@ namespace {
 
 int E_(const vsim_model *m) { return m->hp.n_embd; }
 
+// ---------------------------------------------------------------- scratch
+// Every scratch allocation for n tokens, in allocation order: where the pointer lives, its
+// bytes (0: not allocated at this n), and how it is allocated and treated.
+enum { S_PINNED = 1, S_ZERO = 2, S_POISON = 4 };  // pinned host memory; zero-filled; NaN-filled by debug_poison
+struct ScratchBuf {
+  void **p;
+  size_t bytes;
+  int flags;
+};
+
+// The tail LayerNorm's block, one allocation at lnt_ep: epoch (own 256-byte line), og [E],
+// jg [E], rec [2 E/32], the heads' flags.  carve_lnt points the views into it (null with it).
+size_t lnt_bytes(size_t E) {
+  return 256 + 2 * E * sizeof(unsigned long long) + 2 * (E / QK) * sizeof(uint4) +
+         TAIL_MAX_HEADS * sizeof(unsigned long long);
+}
+void carve_lnt(vsim_model *m) {
+  const size_t E = E_(m);
+  uint8_t *p = (uint8_t *)m->lnt_ep;
+  m->lnt_og = p ? (unsigned long long *)(p + 256) : nullptr;
+  m->lnt_jg = p ? m->lnt_og + E : nullptr;
+  m->lnt_rec = p ? (uint4 *)(m->lnt_jg + E) : nullptr;
+  m->tail_hflag = p ? (unsigned long long *)(m->lnt_rec + 2 * (E / QK)) : nullptr;
+}
+
+std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
+  const size_t E = E_(m), F = 4 * E, V = m->hp.n_vocab, H = m->hp.n_head, f = sizeof(float);
+  const size_t d = E / H, nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
+  // counters of the fused layer kernels at [0], [64], [128] (separate 256-byte lines)
+  // (k_layer_exact: one set per layer, [il - l0][256], zeroed by a memset node per token)
+  const size_t ncnt = (size_t)std::max(1, m->l1 - m->l0) * 256;
+  std::vector<ScratchBuf> t;
+  auto add = [&](auto **p, size_t bytes, int flags = 0) { t.push_back({(void **)p, bytes, flags}); };
+  auto q4 = [&](size_t k) { return n * k / QK * QBYTES; };  // n activation rows of k values, Q4_0
+  for (float **p : {&m->inpL, &m->cur1, &m->cur2, &m->Qb, &m->Kb, &m->Vb, &m->attn_in, &m->attn, &m->ff})
+    add(p, n * E * f, S_POISON);
+  add(&m->fch, n * F * f, S_POISON);
+  add(&m->kq, n * H * m->n_ctx * f, S_POISON);
+  add(&m->logits, V * f, S_POISON);
+  add(&m->xq1, q4(E), S_POISON);
+  add(&m->xq2, q4(E), S_POISON);
+  add(&m->xq3, q4(F), S_POISON);
+  add(&m->xd1, n * E * f, S_POISON);
+  add(&m->xd2, n * E * f, S_POISON);
+  add(&m->xd3, n * F * f, S_POISON);
+  add(&m->tok_dev, n * sizeof(int32_t));
+  add(&m->tok_host, n * sizeof(int32_t), S_PINNED);
+  add(&m->logit_host, V * f, S_PINNED);
+  add(&m->xqa, q4(E), S_POISON);
+  add(&m->xda, n * E * f, S_POISON);
+  add(&m->inpL2, E * f, S_POISON);
+  add(&m->npast_dev, sizeof(int));
+  add(&m->npast_host, sizeof(int), S_PINNED);
+  add(&m->am_dev, sizeof(int));
+  add(&m->am_ws, 2 * sizeof(unsigned long long), S_ZERO);
+  add(&m->am_host, sizeof(int), S_PINNED);
+  add(&m->hist_dev, (size_t)m->n_ctx * sizeof(int));
+  add(&m->tail_done, ncnt * sizeof(unsigned), S_ZERO);
+  add(&m->lnt_ep, lnt_bytes(E), S_ZERO);  // one allocation, carved by carve_lnt
+  add(&m->fast_ffp, 8 * E * f);
+  add(&m->pf_x16, n >= (size_t)GEMM_MIN_N ? n * (E + F) * sizeof(uint16_t) : 0, S_POISON);
+  add(&m->fast_part, H * nch * (d + 2) * f, S_ZERO);  // finite stale values
+  return t;
+}
+
+void drop(StepGraph &g) {
+  if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  if (g.graph) (void)hipGraphDestroy(g.graph);
+  g = StepGraph{};
+}
+
 void free_scratch(vsim_model *m) {
-  void *ps[] = {m->inpL, m->cur1, m->cur2, m->Qb, m->Kb, m->Vb, m->attn_in, m->attn, m->ff, m->fch, m->kq,
-                m->logits, m->xq1, m->xq2, m->xq3, m->xd1, m->xd2, m->xd3, m->tok_dev};
-  for (void *p : ps)
-    if (p) (void)hipFree(p);
-  if (m->tok_host) (void)hipHostFree(m->tok_host);
-  if (m->logit_host) (void)hipHostFree(m->logit_host);
-  if (m->gexec) (void)hipGraphExecDestroy(m->gexec);
-  if (m->graph) (void)hipGraphDestroy(m->graph);
-  if (m->gexec_am) (void)hipGraphExecDestroy(m->gexec_am);
-  if (m->graph_am) (void)hipGraphDestroy(m->graph_am);
-  if (m->am_dev) (void)hipFree(m->am_dev);
-  if (m->am_ws) (void)hipFree(m->am_ws);
-  m->am_ws = nullptr;
-  if (m->am_host) (void)hipHostFree(m->am_host);
-  m->gexec_am = nullptr;
-  m->graph_am = nullptr;
-  m->graph_am_mode = -1;
-  m->am_dev = m->am_host = nullptr;
-  if (m->gexec_gen) (void)hipGraphExecDestroy(m->gexec_gen);
-  if (m->graph_gen) (void)hipGraphDestroy(m->graph_gen);
-  if (m->hist_dev) (void)hipFree(m->hist_dev);
-  if (m->tail_done) (void)hipFree(m->tail_done);
-  m->tail_done = nullptr;
-  if (m->lnt_ep) (void)hipFree(m->lnt_ep);
-  m->lnt_ep = nullptr;
-  m->lnt_og = m->lnt_jg = nullptr;
-  m->lnt_rec = nullptr;
-  m->tail_hflag = nullptr;
+  for (StepGraph &g : m->step) drop(g);  // they hold the scratch addresses
+  for (const ScratchBuf &b : scratch_table(m, m->n_max)) {
+    if (*b.p) (void)(b.flags & S_PINNED ? hipHostFree(*b.p) : hipFree(*b.p));
+    *b.p = nullptr;
+  }
+  carve_lnt(m);
   if (m->pf_scratch) (void)hipFree(m->pf_scratch);
   m->pf_scratch = nullptr;
-  if (m->pf_x16) (void)hipFree(m->pf_x16);
-  m->pf_x16 = nullptr;
   m->pf_bytes = 0;
-  if (m->fast_ffp) (void)hipFree(m->fast_ffp);
-  if (m->fast_part) (void)hipFree(m->fast_part);
-  m->fast_ffp = m->fast_part = nullptr;
-  m->gexec_gen = nullptr;
-  m->graph_gen = nullptr;
-  m->graph_gen_mode = -1;
-  m->hist_dev = nullptr;
-  if (m->gexec_st) (void)hipGraphExecDestroy(m->gexec_st);
-  if (m->graph_st) (void)hipGraphDestroy(m->graph_st);
-  m->gexec_st = nullptr;
-  m->graph_st = nullptr;
-  m->graph_st_mode = -1;
-  if (m->xqa) (void)hipFree(m->xqa);
-  if (m->xda) (void)hipFree(m->xda);
-  if (m->inpL2) (void)hipFree(m->inpL2);
-  m->inpL2 = nullptr;
-  if (m->npast_dev) (void)hipFree(m->npast_dev);
-  if (m->npast_host) (void)hipHostFree(m->npast_host);
-  m->gexec = nullptr;
-  m->graph = nullptr;
-  m->graph_mode = -1;
-  m->xqa = nullptr;
-  m->xda = nullptr;
-  m->npast_dev = m->npast_host = nullptr;
   m->st_npast = -1;  // the device n_past went with npast_dev: stage_step needs a new stage_begin
-  m->inpL = m->cur1 = m->cur2 = m->Qb = m->Kb = m->Vb = m->attn_in = m->attn = m->ff = m->fch = m->kq = m->logits =
-      nullptr;
-  m->xq1 = m->xq2 = m->xq3 = nullptr;
-  m->xd1 = m->xd2 = m->xd3 = nullptr;
-  m->tok_dev = nullptr;
-  m->tok_host = nullptr;
-  m->logit_host = nullptr;
   m->n_max = 0;
 }
 
@@ -232,150 +253,149 @@ int ensure_scratch(vsim_model *m, int N) {
   VSIM_HIP(hipStreamSynchronize(m->stream));
   free_scratch(m);
   const int n = N < 16 ? 16 : N;
-  const size_t E = E_(m), F = 4 * E, V = m->hp.n_vocab, H = m->hp.n_head;
-  auto fa = [&](float **p, size_t cnt) { return hipMalloc((void **)p, cnt * sizeof(float)); };
-  auto ba = [&](uint8_t **p, size_t k) { return hipMalloc((void **)p, (size_t)n * k / QK * QBYTES); };
-  VSIM_HIP(fa(&m->inpL, n * E));
-  VSIM_HIP(fa(&m->cur1, n * E));
-  VSIM_HIP(fa(&m->cur2, n * E));
-  VSIM_HIP(fa(&m->Qb, n * E));
-  VSIM_HIP(fa(&m->Kb, n * E));
-  VSIM_HIP(fa(&m->Vb, n * E));
-  VSIM_HIP(fa(&m->attn_in, n * E));
-  VSIM_HIP(fa(&m->attn, n * E));
-  VSIM_HIP(fa(&m->ff, n * E));
-  VSIM_HIP(fa(&m->fch, n * F));
-  VSIM_HIP(fa(&m->kq, (size_t)n * H * m->n_ctx));
-  VSIM_HIP(fa(&m->logits, V));
-  VSIM_HIP(ba(&m->xq1, E));
-  VSIM_HIP(ba(&m->xq2, E));
-  VSIM_HIP(ba(&m->xq3, F));
-  VSIM_HIP(fa(&m->xd1, n * E));
-  VSIM_HIP(fa(&m->xd2, n * E));
-  VSIM_HIP(fa(&m->xd3, n * F));
-  VSIM_HIP(hipMalloc((void **)&m->tok_dev, n * sizeof(int32_t)));
-  VSIM_HIP(hipHostMalloc((void **)&m->tok_host, n * sizeof(int32_t), hipHostMallocDefault));
-  VSIM_HIP(hipHostMalloc((void **)&m->logit_host, V * sizeof(float), hipHostMallocDefault));
-  VSIM_HIP(ba(&m->xqa, E));
-  VSIM_HIP(fa(&m->xda, n * E));
-  VSIM_HIP(fa(&m->inpL2, E));
-  VSIM_HIP(hipMalloc((void **)&m->npast_dev, sizeof(int)));
-  VSIM_HIP(hipHostMalloc((void **)&m->npast_host, sizeof(int), hipHostMallocDefault));
-  VSIM_HIP(hipMalloc((void **)&m->am_dev, sizeof(int)));
-  VSIM_HIP(hipMalloc((void **)&m->am_ws, 2 * sizeof(unsigned long long)));
-  VSIM_HIP(hipMemset(m->am_ws, 0, 2 * sizeof(unsigned long long)));
-  VSIM_HIP(hipHostMalloc((void **)&m->am_host, sizeof(int), hipHostMallocDefault));
-  VSIM_HIP(hipMalloc((void **)&m->hist_dev, (size_t)m->n_ctx * sizeof(int)));
-  // counters of the fused layer kernels at [0], [64], [128] (separate 256-byte lines)
-  // (k_layer_exact: one set per layer, [il - l0][256], zeroed by a memset node per token)
-  const size_t ncnt = (size_t)std::max(1, m->l1 - m->l0) * 256;
-  VSIM_HIP(hipMalloc((void **)&m->tail_done, ncnt * sizeof(unsigned)));
-  VSIM_HIP(hipMemset(m->tail_done, 0, ncnt * sizeof(unsigned)));
-  {
-    // one allocation: epoch (own 256-byte line), og [E], jg [E], rec [2 E/32], the heads' flags
-    const size_t lb = 256 + 2 * E * sizeof(unsigned long long) + 2 * (E / QK) * sizeof(uint4) +
-                      TAIL_MAX_HEADS * sizeof(unsigned long long);
-    uint8_t *p = nullptr;
-    VSIM_HIP(hipMalloc((void **)&p, lb));
-    VSIM_HIP(hipMemset(p, 0, lb));
-    m->lnt_ep = (unsigned *)p;
-    m->lnt_og = (unsigned long long *)(p + 256);
-    m->lnt_jg = m->lnt_og + E;
-    m->lnt_rec = (uint4 *)(m->lnt_jg + E);
-    m->tail_hflag = (unsigned long long *)(m->lnt_rec + 2 * (E / QK));
+  for (const ScratchBuf &b : scratch_table(m, n)) {
+    if (!b.bytes) continue;
+    if (b.flags & S_PINNED)
+      VSIM_HIP(hipHostMalloc(b.p, b.bytes, hipHostMallocDefault));
+    else
+      VSIM_HIP(hipMalloc(b.p, b.bytes));
+    if (b.flags & S_ZERO) VSIM_HIP(hipMemset(*b.p, 0, b.bytes));
   }
-  {
-    const size_t d = E / H, nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
-    VSIM_HIP(fa(&m->fast_ffp, 8 * E));
-    if (n >= GEMM_MIN_N) VSIM_HIP(hipMalloc(&m->pf_x16, (size_t)n * (E + F) * sizeof(uint16_t)));
-    VSIM_HIP(fa(&m->fast_part, H * nch * (d + 2)));
-    VSIM_HIP(hipMemset(m->fast_part, 0, H * nch * (d + 2) * sizeof(float)));  // finite stale values
-  }
+  carve_lnt(m);
   m->n_max = n;
   return VSIM_OK;
 }
 
-// Register every tensor this stage owns, with its ggml-file name and byte size.
-void plan_slots(vsim_model *m, std::vector<std::pair<std::string, Slot>> &out) {
-  const int E = m->hp.n_embd, V = m->hp.n_vocab, F = 4 * E;
-  auto q = [&](const std::string &n, int rows, int k, int layer) { out.push_back({n, Slot{nullptr, KQ4, rows, k, layer, false}}); };
-  auto f = [&](const std::string &n, int k, int layer) { out.push_back({n, Slot{nullptr, KF32, 1, k, layer, false}}); };
-  if (m->arch == VSIM_ARCH_GPTNEOX) {
-    if (m->first) q("gpt_neox.embed_in.weight", V, E, -1);
-    if (m->last) {
-      f("gpt_neox.final_layer_norm.weight", E, -1);
-      f("gpt_neox.final_layer_norm.bias", E, -1);
-      q("embed_out.weight", V, E, -1);
-    }
-    for (int i = m->l0; i < m->l1; ++i) {
-      const std::string p = "gpt_neox.layers." + std::to_string(i) + ".";
-      f(p + "input_layernorm.weight", E, i);
-      f(p + "input_layernorm.bias", E, i);
-      f(p + "post_attention_layernorm.weight", E, i);
-      f(p + "post_attention_layernorm.bias", E, i);
-      q(p + "attention.query.weight", E, E, i);
-      f(p + "attention.query.bias", E, i);
-      q(p + "attention.key.weight", E, E, i);
-      f(p + "attention.key.bias", E, i);
-      q(p + "attention.value.weight", E, E, i);
-      f(p + "attention.value.bias", E, i);
-      q(p + "attention.dense.weight", E, E, i);
-      f(p + "attention.dense.bias", E, i);
-      q(p + "mlp.dense_h_to_4h.weight", F, E, i);
-      f(p + "mlp.dense_h_to_4h.bias", F, i);
-      q(p + "mlp.dense_4h_to_h.weight", E, F, i);
-      f(p + "mlp.dense_4h_to_h.bias", E, i);
-    }
-  } else if (m->arch == VSIM_ARCH_BLOOM) {  // convert_bloom_to_ggml.py:22-34 names
-    if (m->first) {
-      q("tok_embeddings.weight", V, E, -1);
-      f("norm.weight", E, -1);
-      f("norm.bias", E, -1);
-    }
-    if (m->last) {
-      f("output_norm.weight", E, -1);
-      f("output_norm.bias", E, -1);
-      q("output.weight", V, E, -1);
-    }
-    for (int i = m->l0; i < m->l1; ++i) {
-      const std::string p = "layers." + std::to_string(i) + ".";
-      f(p + "attention_norm.weight", E, i);
-      f(p + "attention_norm.bias", E, i);
-      q(p + "attention.query_key_value.weight/q", E, E, i);  // the file tensor's row blocks
-      q(p + "attention.query_key_value.weight/k", E, E, i);
-      q(p + "attention.query_key_value.weight/v", E, E, i);
-      f(p + "attention.query_key_value.bias", 3 * E, i);
-      q(p + "attention.wo.weight", E, E, i);
-      f(p + "attention.wo.bias", E, i);
-      f(p + "ffn_norm.weight", E, i);
-      f(p + "ffn_norm.bias", E, i);
-      q(p + "feed_forward.w1.weight", F, E, i);
-      f(p + "feed_forward.w1.bias", F, i);
-      q(p + "feed_forward.w2.weight", E, F, i);
-      f(p + "feed_forward.w2.bias", E, i);
-    }
-  } else {
-    if (m->first) q("transformer.wte.weight", V, E, -1);
-    if (m->last) {
-      f("transformer.ln_f.weight", E, -1);
-      f("transformer.ln_f.bias", E, -1);
-      q("lm_head.weight", V, E, -1);
-      f("lm_head.bias", V, -1);
-    }
-    for (int i = m->l0; i < m->l1; ++i) {
-      const std::string p = "transformer.h." + std::to_string(i) + ".";
-      f(p + "ln_1.weight", E, i);
-      f(p + "ln_1.bias", E, i);
-      q(p + "attn.q_proj.weight", E, E, i);
-      q(p + "attn.k_proj.weight", E, E, i);
-      q(p + "attn.v_proj.weight", E, E, i);
-      q(p + "attn.out_proj.weight", E, E, i);
-      q(p + "mlp.fc_in.weight", F, E, i);
-      f(p + "mlp.fc_in.bias", F, i);
-      q(p + "mlp.fc_out.weight", E, F, i);
-      f(p + "mlp.fc_out.bias", E, i);
-    }
+// fast prefill's fp16 K / V^T copies, allocated on first need (prompt evals are never
+// graph-captured: allocating there is safe)
+int ensure_pf_scratch(vsim_model *m) {
+  if (m->pf_scratch) return VSIM_OK;
+  m->pf_bytes = attn_prefill_scratch(E_(m), m->n_ctx);
+  VSIM_HIP(hipMalloc(&m->pf_scratch, m->pf_bytes));
+  return VSIM_OK;
+}
+
+// the scales of a Q4 SoA activation row of k values: they follow its 16-byte quants
+float *q4_scales(uint8_t *q, int k) { return (float *)(q + (size_t)(k / QK) * 16); }
+
+// ---------------------------------------------------------------- tensors
+// One row per tensor of an architecture: where its device pointer lives (a LayerW member, or
+// a model member for the globals), its ggml-file name (globals) or the suffix after the layer
+// prefix, and its shape -- Q4: rows x k; F32: k elements.  A global belongs to the first or the
+// last stage.
+enum Dim { D_E, D_4E, D_V, D_3E };
+struct TensorRow {
+  const char *name;
+  Dim rows, k;
+  void *LayerW::*lq;  // exactly one of the four targets is set: layer / global, Q4 / F32
+  float *LayerW::*lf;
+  void *vsim_model::*gq;
+  float *vsim_model::*gf;
+  bool first;
+  int kind() const { return lq || gq ? KQ4 : KF32; }
+};
+TensorRow row(void *LayerW::*p, const char *n, Dim rows, Dim k) { return {n, rows, k, p, nullptr, nullptr, nullptr, false}; }
+TensorRow row(float *LayerW::*p, const char *n, Dim k) { return {n, D_E, k, nullptr, p, nullptr, nullptr, false}; }
+TensorRow row(void *vsim_model::*p, const char *n, Dim rows, Dim k, bool first) {
+  return {n, rows, k, nullptr, nullptr, p, nullptr, first};
+}
+TensorRow row(float *vsim_model::*p, const char *n, Dim k, bool first) {
+  return {n, D_E, k, nullptr, nullptr, nullptr, p, first};
+}
+
+struct ArchTable {
+  const char *layer_prefix;  // + layer index + "." + the row's suffix
+  std::vector<TensorRow> globals, layer;
+};
+
+const ArchTable &arch_table(int arch) {
+  using M = vsim_model;
+  using L = LayerW;
+  const bool FIRST = true, LAST = false;
+  static const ArchTable neox = {
+      "gpt_neox.layers.",
+      {row(&M::wte, "gpt_neox.embed_in.weight", D_V, D_E, FIRST),
+       row(&M::lnf_w, "gpt_neox.final_layer_norm.weight", D_E, LAST),
+       row(&M::lnf_b, "gpt_neox.final_layer_norm.bias", D_E, LAST),
+       row(&M::lmh, "embed_out.weight", D_V, D_E, LAST)},
+      {row(&L::ln1_w, "input_layernorm.weight", D_E),
+       row(&L::ln1_b, "input_layernorm.bias", D_E),
+       row(&L::ln2_w, "post_attention_layernorm.weight", D_E),
+       row(&L::ln2_b, "post_attention_layernorm.bias", D_E),
+       row(&L::wq, "attention.query.weight", D_E, D_E),
+       row(&L::bq, "attention.query.bias", D_E),
+       row(&L::wk, "attention.key.weight", D_E, D_E),
+       row(&L::bk, "attention.key.bias", D_E),
+       row(&L::wv, "attention.value.weight", D_E, D_E),
+       row(&L::bv, "attention.value.bias", D_E),
+       row(&L::wo, "attention.dense.weight", D_E, D_E),
+       row(&L::bo, "attention.dense.bias", D_E),
+       row(&L::wfc, "mlp.dense_h_to_4h.weight", D_4E, D_E),
+       row(&L::bfc, "mlp.dense_h_to_4h.bias", D_4E),
+       row(&L::wproj, "mlp.dense_4h_to_h.weight", D_E, D_4E),
+       row(&L::bproj, "mlp.dense_4h_to_h.bias", D_E)}};
+  static const ArchTable bloom = {  // convert_bloom_to_ggml.py:22-34 names
+      "layers.",
+      {row(&M::wte, "tok_embeddings.weight", D_V, D_E, FIRST),
+       row(&M::emb_w, "norm.weight", D_E, FIRST),
+       row(&M::emb_b, "norm.bias", D_E, FIRST),
+       row(&M::lnf_w, "output_norm.weight", D_E, LAST),
+       row(&M::lnf_b, "output_norm.bias", D_E, LAST),
+       row(&M::lmh, "output.weight", D_V, D_E, LAST)},
+      {row(&L::ln1_w, "attention_norm.weight", D_E),
+       row(&L::ln1_b, "attention_norm.bias", D_E),
+       row(&L::wq, "attention.query_key_value.weight/q", D_E, D_E),  // the file tensor's row blocks
+       row(&L::wk, "attention.query_key_value.weight/k", D_E, D_E),
+       row(&L::wv, "attention.query_key_value.weight/v", D_E, D_E),
+       row(&L::bq, "attention.query_key_value.bias", D_3E),  // bk, bv: views into it (bind_pointers)
+       row(&L::wo, "attention.wo.weight", D_E, D_E),
+       row(&L::bo, "attention.wo.bias", D_E),
+       row(&L::ln2_w, "ffn_norm.weight", D_E),
+       row(&L::ln2_b, "ffn_norm.bias", D_E),
+       row(&L::wfc, "feed_forward.w1.weight", D_4E, D_E),
+       row(&L::bfc, "feed_forward.w1.bias", D_4E),
+       row(&L::wproj, "feed_forward.w2.weight", D_E, D_4E),
+       row(&L::bproj, "feed_forward.w2.bias", D_E)}};
+  static const ArchTable gptj = {
+      "transformer.h.",
+      {row(&M::wte, "transformer.wte.weight", D_V, D_E, FIRST),
+       row(&M::lnf_w, "transformer.ln_f.weight", D_E, LAST),
+       row(&M::lnf_b, "transformer.ln_f.bias", D_E, LAST),
+       row(&M::lmh, "lm_head.weight", D_V, D_E, LAST),
+       row(&M::lmh_b, "lm_head.bias", D_V, LAST)},
+      {row(&L::ln1_w, "ln_1.weight", D_E),
+       row(&L::ln1_b, "ln_1.bias", D_E),
+       row(&L::wq, "attn.q_proj.weight", D_E, D_E),
+       row(&L::wk, "attn.k_proj.weight", D_E, D_E),
+       row(&L::wv, "attn.v_proj.weight", D_E, D_E),
+       row(&L::wo, "attn.out_proj.weight", D_E, D_E),
+       row(&L::wfc, "mlp.fc_in.weight", D_4E, D_E),
+       row(&L::bfc, "mlp.fc_in.bias", D_4E),
+       row(&L::wproj, "mlp.fc_out.weight", D_E, D_4E),
+       row(&L::bproj, "mlp.fc_out.bias", D_E)}};
+  return arch == VSIM_ARCH_GPTNEOX ? neox : arch == VSIM_ARCH_BLOOM ? bloom : gptj;
+}
+
+// fn(ggml name, row, layer or -1) for every tensor this stage owns: the first stage's globals,
+// the last stage's, then layer by layer
+template <class Fn>
+void for_each_tensor(const vsim_model *m, Fn fn) {
+  const ArchTable &t = arch_table(m->arch);
+  for (const TensorRow &r : t.globals)
+    if (r.first ? m->first : m->last) fn(std::string(r.name), r, -1);
+  for (int i = m->l0; i < m->l1; ++i) {
+    const std::string p = t.layer_prefix + std::to_string(i) + ".";
+    for (const TensorRow &r : t.layer) fn(p + r.name, r, i);
   }
+}
+
+// Register every tensor this stage owns, with its ggml-file name and shape.
+void plan_slots(vsim_model *m, std::vector<std::pair<std::string, Slot>> &out) {
+  const int E = m->hp.n_embd;
+  auto dim = [&](Dim d) { return d == D_E ? E : d == D_4E ? 4 * E : d == D_3E ? 3 * E : m->hp.n_vocab; };
+  for_each_tensor(m, [&](const std::string &n, const TensorRow &r, int layer) {
+    out.push_back({n, Slot{nullptr, r.kind(), r.kind() == KQ4 ? dim(r.rows) : 1, dim(r.k), layer, false}});
+  });
 }
 
 // bytes of the tensor in the ggml file (AoS blocks) and on the device (W4T32, padded)
@@ -385,86 +405,28 @@ size_t slot_bytes(const Slot &s) {
 size_t slot_dev_bytes(const Slot &s) { return s.kind == KQ4 ? w4_bytes(s.rows, s.k) : (size_t)s.k * sizeof(float); }
 
 void bind_pointers(vsim_model *m) {
-  auto P = [&](const std::string &n) -> void * {
-    auto it = m->slots.find(n);
-    return it == m->slots.end() ? nullptr : it->second.ptr;
-  };
-  auto F = [&](const std::string &n) { return (float *)P(n); };
   m->layers.assign(m->l1 - m->l0, LayerW{});
-  if (m->arch == VSIM_ARCH_GPTNEOX) {
-    m->wte = P("gpt_neox.embed_in.weight");
-    m->lnf_w = F("gpt_neox.final_layer_norm.weight");
-    m->lnf_b = F("gpt_neox.final_layer_norm.bias");
-    m->lmh = P("embed_out.weight");
-    for (int i = m->l0; i < m->l1; ++i) {
-      LayerW &L = m->layers[i - m->l0];
-      const std::string p = "gpt_neox.layers." + std::to_string(i) + ".";
-      L.ln1_w = F(p + "input_layernorm.weight");
-      L.ln1_b = F(p + "input_layernorm.bias");
-      L.ln2_w = F(p + "post_attention_layernorm.weight");
-      L.ln2_b = F(p + "post_attention_layernorm.bias");
-      L.wq = P(p + "attention.query.weight");
-      L.bq = F(p + "attention.query.bias");
-      L.wk = P(p + "attention.key.weight");
-      L.bk = F(p + "attention.key.bias");
-      L.wv = P(p + "attention.value.weight");
-      L.bv = F(p + "attention.value.bias");
-      L.wo = P(p + "attention.dense.weight");
-      L.bo = F(p + "attention.dense.bias");
-      L.wfc = P(p + "mlp.dense_h_to_4h.weight");
-      L.bfc = F(p + "mlp.dense_h_to_4h.bias");
-      L.wproj = P(p + "mlp.dense_4h_to_h.weight");
-      L.bproj = F(p + "mlp.dense_4h_to_h.bias");
+  for_each_tensor(m, [&](const std::string &n, const TensorRow &r, int layer) {
+    auto it = m->slots.find(n);
+    void *p = it == m->slots.end() ? nullptr : it->second.ptr;
+    if (r.gq) m->*r.gq = p;
+    if (r.gf) m->*r.gf = (float *)p;
+    if (r.lq) m->layers[layer - m->l0].*r.lq = p;
+    if (r.lf) m->layers[layer - m->l0].*r.lf = (float *)p;
+  });
+  if (m->arch == VSIM_ARCH_BLOOM)  // q | k | v of the one query_key_value bias vector
+    for (LayerW &L : m->layers) {
+      L.bk = L.bq + m->hp.n_embd;
+      L.bv = L.bq + 2 * m->hp.n_embd;
     }
-  } else if (m->arch == VSIM_ARCH_BLOOM) {
-    m->wte = P("tok_embeddings.weight");
-    m->emb_w = F("norm.weight");
-    m->emb_b = F("norm.bias");
-    m->lnf_w = F("output_norm.weight");
-    m->lnf_b = F("output_norm.bias");
-    m->lmh = P("output.weight");
-    const int E = m->hp.n_embd;
-    for (int i = m->l0; i < m->l1; ++i) {
-      LayerW &L = m->layers[i - m->l0];
-      const std::string p = "layers." + std::to_string(i) + ".";
-      L.ln1_w = F(p + "attention_norm.weight");
-      L.ln1_b = F(p + "attention_norm.bias");
-      L.ln2_w = F(p + "ffn_norm.weight");
-      L.ln2_b = F(p + "ffn_norm.bias");
-      L.wq = P(p + "attention.query_key_value.weight/q");
-      L.wk = P(p + "attention.query_key_value.weight/k");
-      L.wv = P(p + "attention.query_key_value.weight/v");
-      L.bq = F(p + "attention.query_key_value.bias");
-      L.bk = L.bq + E;
-      L.bv = L.bq + 2 * E;
-      L.wo = P(p + "attention.wo.weight");
-      L.bo = F(p + "attention.wo.bias");
-      L.wfc = P(p + "feed_forward.w1.weight");
-      L.bfc = F(p + "feed_forward.w1.bias");
-      L.wproj = P(p + "feed_forward.w2.weight");
-      L.bproj = F(p + "feed_forward.w2.bias");
-    }
-  } else {
-    m->wte = P("transformer.wte.weight");
-    m->lnf_w = F("transformer.ln_f.weight");
-    m->lnf_b = F("transformer.ln_f.bias");
-    m->lmh = P("lm_head.weight");
-    m->lmh_b = F("lm_head.bias");
-    for (int i = m->l0; i < m->l1; ++i) {
-      LayerW &L = m->layers[i - m->l0];
-      const std::string p = "transformer.h." + std::to_string(i) + ".";
-      L.ln1_w = F(p + "ln_1.weight");
-      L.ln1_b = F(p + "ln_1.bias");
-      L.wq = P(p + "attn.q_proj.weight");
-      L.wk = P(p + "attn.k_proj.weight");
-      L.wv = P(p + "attn.v_proj.weight");
-      L.wo = P(p + "attn.out_proj.weight");
-      L.wfc = P(p + "mlp.fc_in.weight");
-      L.bfc = F(p + "mlp.fc_in.bias");
-      L.wproj = P(p + "mlp.fc_out.weight");
-      L.bproj = F(p + "mlp.fc_out.bias");
-    }
-  }
+}
+
+// BLOOM's fused query_key_value weight: one file tensor, three [E][E] row blocks q | k | v,
+// each a slot of its own (name + QKV_PARTS[i])
+const char *const QKV_PARTS[3] = {"/q", "/k", "/v"};
+bool is_fused_qkv(const vsim_model *m, const std::string &n) {
+  const std::string suf = "attention.query_key_value.weight";
+  return m->arch == VSIM_ARCH_BLOOM && n.size() >= suf.size() && n.compare(n.size() - suf.size(), suf.size(), suf) == 0;
 }
 
 #define RC(x)                    \
@@ -544,6 +506,16 @@ int prof_collect(vsim_model *m) {
   return VSIM_OK;
 }
 
+// One launch between its profiling brackets, counted into nk.  A macro so that the name (some
+// are built as std::string) and the bytes are evaluated only when profiling is on.
+#define LAUNCH(m, nk, call, name, bytes)                   \
+  do {                                                     \
+    const long ev_ = prof_begin(m);                        \
+    RC(call);                                              \
+    if (ev_ >= 0) prof_end(m, ev_, name, bytes);           \
+    ++nk;                                                  \
+  } while (0)
+
 double w4_algo_bytes(const W4 &w) { return (double)w.rows * w.k / QK * QBYTES; }
 
 // Quantize an activation and run one GEMV in the model's mode.  x16 non-null (fast-mode
@@ -562,23 +534,18 @@ int mm(vsim_model *m, const void *W, int M, int K, const float *x, int N, uint8_
   // long prompt: the 256-wide-tile GEMM, the Q4_0 weight dequantized to fp16 in LDS
   if (x16 && N >= G2_MIN_N && K % 64 == 0) {
     const bool gelu = gq && gq_bias && M % QK == 0;
-    const long ev = prof_begin(m);
-    RC(launch_gemm_q4_256(w4_view(W, M, K), x16, N, gelu ? gq_bias : bias, y, m->stream, gelu ? gq : nullptr,
-                          gelu ? nullptr : epi));
-    prof_end(m, ev, "k_gemm_f16_256 (prompt)", (double)M * K / QK * QBYTES);
-    ++nk;
+    LAUNCH(m, nk,
+           launch_gemm_q4_256(w4_view(W, M, K), x16, N, gelu ? gq_bias : bias, y, m->stream, gelu ? gq : nullptr,
+                              gelu ? nullptr : epi),
+           "k_gemm_f16_256 (prompt)", (double)M * K / QK * QBYTES);
     if (fused) *fused = gelu || epi;
     return VSIM_OK;
   }
-  const long ev = prof_begin(m);
-  if (x16) {
-    RC(launch_gemm_f16x(w4_view(W, M, K), x16, N, bias, y, m->stream));
-  } else {
-    RC(launch_q4_gemv(W, M, K, xq, xd, N, bias, y, m->mode, m->stream));
-  }
-  prof_end(m, ev, x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
-           (double)M * K / QK * QBYTES);
-  ++nk;
+  LAUNCH(m, nk,
+         x16 ? launch_gemm_f16x(w4_view(W, M, K), x16, N, bias, y, m->stream)
+             : launch_q4_gemv(W, M, K, xq, xd, N, bias, y, m->mode, m->stream),
+         x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
+         (double)M * K / QK * QBYTES);
   return VSIM_OK;
 }
 
@@ -676,10 +643,7 @@ int run_layer(vsim_model *m, int il, int n_past, int N, int &nk) {
   // ... and the new keys' fp16 copies for the prompt attention (K rows, V^T columns), which
   // then converts only the cached keys before them
   const bool attn16 = m->mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
-  if (attn16 && !m->pf_scratch) {  // (prompt evals are never graph-captured: allocating here is safe)
-    m->pf_bytes = attn_prefill_scratch(E, m->n_ctx);
-    VSIM_HIP(hipMalloc(&m->pf_scratch, m->pf_bytes));
-  }
+  if (attn16) RC(ensure_pf_scratch(m));
   const bool kv16_epi = rope_epi && attn16;
   G2Epi ek = er, ev;
   if (kv16_epi) {
@@ -692,10 +656,8 @@ int run_layer(vsim_model *m, int il, int n_past, int N, int &nk) {
   // Q, K, V (+ bias for GPT-NeoX, vsim.cpp:540-547); a long GPT-J prompt's Q and K (both RoPE
   // epilogues, no bias) as one launch of both tile grids
   if (rope_epi && gemm_pair_enabled(E, E)) {
-    const long ev = prof_begin(m);
-    RC(launch_gemm_q4_256_pair(w4_view(L.wq, E, E), w4_view(L.wk, E, E), X.a, N, m->Qb, kout, er, ek, s));
-    prof_end(m, ev, "k_gemm_f16_256 (prompt)", 2.0 * E * E / QK * QBYTES);
-    ++nk;
+    LAUNCH(m, nk, launch_gemm_q4_256_pair(w4_view(L.wq, E, E), w4_view(L.wk, E, E), X.a, N, m->Qb, kout, er, ek, s),
+           "k_gemm_f16_256 (prompt)", 2.0 * E * E / QK * QBYTES);
   } else {
     RC(mm(m, L.wq, E, E, m->cur1, N, m->xq1, m->xd1, true, gptj ? nullptr : L.bq, m->Qb, nk, X.a, nullptr, nullptr,
           nullptr, rope_epi ? &er : nullptr));
@@ -799,10 +761,8 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
-  const int nbE = E / QK, nbF = F / QK;
   uint8_t *q1 = m->xq1, *q3 = m->xq3;
-  float *d1 = (float *)(q1 + (size_t)nbE * 16), *d2 = (float *)(m->xq2 + (size_t)nbE * 16);
-  float *d3 = (float *)(q3 + (size_t)nbF * 16);
+  float *d1 = q4_scales(q1, E), *d2 = q4_scales(m->xq2, E), *d3 = q4_scales(q3, F);
   if (m->first) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
@@ -842,10 +802,8 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     P.d = d;
     P.n_rot = m->hp.n_rot;
     P.style = gptj ? 1 : 0;
-    long ev = prof_begin(m);
-    RC(launch_fast_gemv(P, E, s));
-    prof_end(m, ev, "k_fast_gemv (fc_in, Q, K, V)", w4_algo_bytes(P.j[0].w) + 3 * w4_algo_bytes(P.j[1].w));
-    ++nk;
+    LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (fc_in, Q, K, V)",
+           w4_algo_bytes(P.j[0].w) + 3 * w4_algo_bytes(P.j[1].w));
     // fc_out split over K | attention chunks
     FastTail T{};
     T.wf = w4_view(L.wproj, E, F);
@@ -864,7 +822,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     T.part = m->fast_part;
     T.hcnt = m->tail_done;
     T.oq_qs = m->xqa;
-    T.oq_d = (float *)(m->xqa + (size_t)(E / QK) * 16);
+    T.oq_d = q4_scales(m->xqa, E);
     // attention merge + out-projection + residual join into the other buffer
     FastOproj O{};
     O.w = w4_view(L.wo, E, E);
@@ -877,14 +835,8 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     O.bproj = L.bproj;
     O.x = R[cur];
     O.out = R[cur ^ 1];
-    ev = prof_begin(m);
-    RC(launch_fast_tail(T, s));
-    prof_end(m, ev, "k_fast_tail (fc_out + attention)", w4_algo_bytes(T.wf) + kv_bytes);
-    ++nk;
-    ev = prof_begin(m);
-    RC(launch_fast_oproj_join(O, s));
-    prof_end(m, ev, "k_fast_oproj_join", w4_algo_bytes(O.w));
-    ++nk;
+    LAUNCH(m, nk, launch_fast_tail(T, s), "k_fast_tail (fc_out + attention)", w4_algo_bytes(T.wf) + kv_bytes);
+    LAUNCH(m, nk, launch_fast_oproj_join(O, s), "k_fast_oproj_join", w4_algo_bytes(O.w));
     cur ^= 1;
   }
   if (m->last) {
@@ -896,10 +848,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     P.xd[0] = P.xd[1] = d1;
     P.nj = 1;
     P.j[0] = FastJob{w4_view(m->lmh, V, E), gptj ? m->lmh_b : nullptr, m->logits, FE_STORE, 0};
-    const long ev = prof_begin(m);
-    RC(launch_fast_gemv(P, E, s));
-    prof_end(m, ev, "k_fast_gemv (lm_head)", w4_algo_bytes(P.j[0].w));
-    ++nk;
+    LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (lm_head)", w4_algo_bytes(P.j[0].w));
   }
   m->resid_final = R[cur];
   return VSIM_OK;
@@ -933,10 +882,8 @@ int enqueue_decode(vsim_model *m, int &nk) {
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
-  const int nbE = E / QK, nbF = F / QK;
   uint8_t *q1 = m->xq1, *q2 = m->xq2, *q3 = m->xq3, *qa = m->xqa;
-  float *d1 = (float *)(q1 + (size_t)nbE * 16), *d2 = (float *)(q2 + (size_t)nbE * 16);
-  float *d3 = (float *)(q3 + (size_t)nbF * 16), *da = (float *)(qa + (size_t)nbE * 16);
+  float *d1 = q4_scales(q1, E), *d2 = q4_scales(q2, E), *d3 = q4_scales(q3, F), *da = q4_scales(qa, E);
   if (m->first && bloom) {  // word embeddings + word_embeddings_layernorm
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->cur1, s));
     RC(launch_norm(m->cur1, m->inpL, E, 1, m->emb_w, m->emb_b, s));
@@ -1022,13 +969,11 @@ int enqueue_decode(vsim_model *m, int &nk) {
     return A;
   };
   auto gemv = [&](const GemvBatch &Bt, const char *what, double bytes) -> int {
-    const long ev = prof_begin(m);
-    RC(launch_gemv_epi(Bt, m->mode, s));
-    if (ev >= 0)
-      prof_end(m, ev, std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : gemv_chain_solo(Bt) ? "k_gemv_solo"
-                                                                                                  : "k_gemv_chain32") +
-                          " (" + what + ")", bytes);
-    ++nk;
+    LAUNCH(m, nk, launch_gemv_epi(Bt, m->mode, s),
+           std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : gemv_chain_solo(Bt) ? "k_gemv_solo"
+                                                                                       : "k_gemv_chain32") +
+               " (" + what + ")",
+           bytes);
     return VSIM_OK;
   };
   for (int il = m->l0; il < m->l1; ++il) {
@@ -1039,10 +984,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
       LnQuantJob j1{R[cur], L.ln1_w, L.ln1_b, q1, d1, m->xd1};
       if (pending) join_into(j1, true);
       if (tail && il == m->l0) j1.ep = m->lnt_ep;  // the step's epoch (the tail's flags)
-      long ev = prof_begin(m);
-      RC(launch_ln_quant(j1, nullptr, E, s));
-      prof_end(m, ev, "k_ln_quant", ln_bytes(1, pending));
-      ++nk;
+      LAUNCH(m, nk, launch_ln_quant(j1, nullptr, E, s), "k_ln_quant", ln_bytes(1, pending));
       if (pending) cur ^= 1;
       // 2. Q, K, V (+ bias; BLOOM: the fused query_key_value's row blocks)
       GemvBatch B{};
@@ -1058,15 +1000,10 @@ int enqueue_decode(vsim_model *m, int &nk) {
       job(Bo, 0, L.wo, E, E, m->xda, qa, da, nullptr, m->attn);
       if (tail) {
         GemvBatch none{};
-        ev = prof_begin(m);
-        RC(launch_layer_tail(none, Bo, A, TailSync{m->tail_hflag, m->lnt_ep, il}, m->n_ctx, s));
-        prof_end(m, ev, "k_layer_tail (attention + out-proj)", w4_algo_bytes(Bo.j[0].w) + kv_bytes);
-        ++nk;
+        LAUNCH(m, nk, launch_layer_tail(none, Bo, A, TailSync{m->tail_hflag, m->lnt_ep, il}, m->n_ctx, s),
+               "k_layer_tail (attention + out-proj)", w4_algo_bytes(Bo.j[0].w) + kv_bytes);
       } else {
-        ev = prof_begin(m);
-        RC(launch_attn_decode(A, m->n_ctx, s));
-        prof_end(m, ev, "k_attn_decode", kv_bytes);
-        ++nk;
+        LAUNCH(m, nk, launch_attn_decode(A, m->n_ctx, s), "k_attn_decode", kv_bytes);
         RC(gemv(Bo, "out-proj", w4_algo_bytes(Bo.j[0].w)));
       }
       // 4. inpFF = (attn + b_o) + x, post-attention LayerNorm + quantize
@@ -1074,10 +1011,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
       j2.ja = m->attn;
       j2.jab = L.bo;
       j2.jout = bloom ? R[cur ^ 1] : nullptr;
-      ev = prof_begin(m);
-      RC(launch_ln_quant(j2, nullptr, E, s));
-      prof_end(m, ev, "k_ln_quant", ln_bytes(1, true));
-      ++nk;
+      LAUNCH(m, nk, launch_ln_quant(j2, nullptr, E, s), "k_ln_quant", ln_bytes(1, true));
       if (bloom) cur ^= 1;
       // 5. fc_in (+ bias, GELU, requantize)   6. fc_out (its bias joins in the next step 1)
       GemvBatch Bi{};
@@ -1101,7 +1035,6 @@ int enqueue_decode(vsim_model *m, int &nk) {
     }
     // 1. (join +) LayerNorm(s) + quantize, unless the previous layer's tail ran them (TailLn)
     const TailSync sy{m->tail_hflag, m->lnt_ep, il};  // the heads' flags of this layer's tail
-    long ev = -1;
     if (!ln_done) {
       LnQuantJob j1{R[cur], L.ln1_w, L.ln1_b, q1, d1, m->xd1};
       LnQuantJob j2{R[cur], L.ln2_w, L.ln2_b, q2, d2, m->xd2};
@@ -1110,10 +1043,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
         join_into(j2, false);
       }
       if (tail && il == m->l0) j1.ep = m->lnt_ep;  // the step's first norm advances the epoch
-      ev = prof_begin(m);
-      RC(launch_ln_quant(j1, gptj ? nullptr : &j2, E, s));
-      prof_end(m, ev, "k_ln_quant", ln_bytes(gptj ? 1 : 2, pending));
-      ++nk;
+      LAUNCH(m, nk, launch_ln_quant(j1, gptj ? nullptr : &j2, E, s), "k_ln_quant", ln_bytes(gptj ? 1 : 2, pending));
       if (pending) cur ^= 1;
     }
     ln_done = false;
@@ -1129,11 +1059,9 @@ int enqueue_decode(vsim_model *m, int &nk) {
     job(B, 1, L.wq, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bq, m->Qb);
     job(B, 2, L.wk, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bk, m->Kb);
     job(B, 3, L.wv, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bv, m->Vb);
-    ev = prof_begin(m);
-    RC(launch_gemv_epi(B, m->mode, s));
-    prof_end(m, ev, m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (fc_in, Q, K, V)" : "k_gemv_fast_epi (fc_in, Q, K, V)",
-             w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w));
-    ++nk;
+    LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
+           m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (fc_in, Q, K, V)" : "k_gemv_fast_epi (fc_in, Q, K, V)",
+           w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w));
     // 3. attention for the new token (attn.hpp), fc_out and the out-projection
     const AttnJob A = attn_job(loff);
     GemvBatch Bf{}, Bo{};
@@ -1173,34 +1101,24 @@ int enqueue_decode(vsim_model *m, int &nk) {
       N.ep = m->lnt_ep;
       N.stats = dev_stats();
       N.il = il;
-      ev = prof_begin(m);
-      RC(launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s, &N));
-      prof_end(m, ev, "k_layer_tail (fc_out + attention + out-proj + join + LayerNorm)",
-               w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes + ln_bytes(N.w2 ? 2 : 1, true));
-      ++nk;
+      LAUNCH(m, nk, launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s, &N),
+             "k_layer_tail (fc_out + attention + out-proj + join + LayerNorm)",
+             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes + ln_bytes(N.w2 ? 2 : 1, true));
       cur ^= 1;
       ln_done = true;
       pending = false;
       continue;
     }
     if (tail) {
-      ev = prof_begin(m);
-      RC(launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s));
-      prof_end(m, ev, "k_layer_tail (fc_out + attention + out-proj)",
-               w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes);
-      ++nk;
+      LAUNCH(m, nk, launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s), "k_layer_tail (fc_out + attention + out-proj)",
+             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes);
     } else {
-      ev = prof_begin(m);
-      RC(launch_attn_decode(A, m->n_ctx, s));
-      prof_end(m, ev, "k_attn_decode", kv_bytes);
-      ++nk;
+      LAUNCH(m, nk, launch_attn_decode(A, m->n_ctx, s), "k_attn_decode", kv_bytes);
       Bf.j[1] = Bo.j[0];
       Bf.nj = 2;
-      ev = prof_begin(m);
-      RC(launch_gemv_epi(Bf, m->mode, s));
-      prof_end(m, ev, m->mode == VSIM_MODE_EXACT ? "k_gemv_chain32 (fc_out, out-proj)" : "k_gemv_fast_epi (fc_out, out-proj)",
-               w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bf.j[1].w));
-      ++nk;
+      LAUNCH(m, nk, launch_gemv_epi(Bf, m->mode, s),
+             m->mode == VSIM_MODE_EXACT ? "k_gemv_chain32 (fc_out, out-proj)" : "k_gemv_fast_epi (fc_out, out-proj)",
+             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bf.j[1].w));
     }
     pending = true;
     pend_a = m->attn;
@@ -1211,20 +1129,14 @@ int enqueue_decode(vsim_model *m, int &nk) {
     if (!ln_done) {
       LnQuantJob jf{R[cur], m->lnf_w, m->lnf_b, q1, d1, m->xd1};
       if (pending) join_into(jf, true);
-      long ev = prof_begin(m);
-      RC(launch_ln_quant(jf, nullptr, E, s));
-      prof_end(m, ev, "k_ln_quant", ln_bytes(1, pending));
-      ++nk;
+      LAUNCH(m, nk, launch_ln_quant(jf, nullptr, E, s), "k_ln_quant", ln_bytes(1, pending));
       if (pending) cur ^= 1;
     }
     GemvBatch B{};
     B.nj = 1;
     job(B, 0, m->lmh, V, E, m->xd1, q1, d1, gptj ? m->lmh_b : nullptr, m->logits);
-    const long ev = prof_begin(m);
-    RC(launch_gemv_epi(B, m->mode, s));
-    prof_end(m, ev, m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (lm_head)" : "k_gemv_fast_epi (lm_head)",
-             w4_algo_bytes(B.j[0].w));
-    ++nk;
+    LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
+           m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (lm_head)" : "k_gemv_fast_epi (lm_head)", w4_algo_bytes(B.j[0].w));
   } else if (pending) {
     RC(launch_residual_join(R[cur], pend_a, pend_ab, m->ff, pend_fb, R[cur ^ 1], E, s));
     ++nk;
@@ -1233,9 +1145,6 @@ int enqueue_decode(vsim_model *m, int &nk) {
   m->resid_final = R[cur];
   return VSIM_OK;
 }
-
-// every graph has a single-token step (the serial-residual ones with 6 launches per layer)
-bool fused_ok(const vsim_model *, int N) { return N == 1; }
 
 thread_local std::string t_err;
 
@@ -1378,7 +1287,7 @@ int model_set_attn(vsim_model *m, int kqv_nth, float scale) {
   VSIM_HIP(hipStreamSynchronize(m->stream));
   m->kqv_nth = kqv_nth;
   m->attn_scale = scale;
-  m->graph_mode = m->graph_am_mode = m->graph_gen_mode = m->graph_st_mode = -1;  // recapture on next use
+  for (StepGraph &g : m->step) g.mode = -1;  // recapture on next use
   return VSIM_OK;
 }
 }  // namespace vsim
@@ -1410,15 +1319,11 @@ void vsim_model_free(vsim_model *m) {
 
 int vsim_model_set_tensor(vsim_model *m, const char *name, const void *host, size_t nbytes) {
   if (m->borrowed) { set_error("set_tensor: the weights belong to the graph executor"); return VSIM_EINVAL; }
-  {  // BLOOM's fused query_key_value weight: three [E][E] row blocks, q | k | v
-    const std::string n(name), suf = "attention.query_key_value.weight";
-    if (m->arch == VSIM_ARCH_BLOOM && n.size() >= suf.size() && n.compare(n.size() - suf.size(), suf.size(), suf) == 0) {
-      const char *parts[3] = {"/q", "/k", "/v"};
-      if (nbytes % 3 != 0) { set_error("set_tensor: fused qkv size"); return VSIM_EINVAL; }
-      for (int i = 0; i < 3; ++i)
-        RC(vsim_model_set_tensor(m, (n + parts[i]).c_str(), (const uint8_t *)host + i * (nbytes / 3), nbytes / 3));
-      return VSIM_OK;
-    }
+  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks, q | k | v
+    if (nbytes % 3 != 0) { set_error("set_tensor: fused qkv size"); return VSIM_EINVAL; }
+    for (int i = 0; i < 3; ++i)
+      RC(vsim_model_set_tensor(m, (n + QKV_PARTS[i]).c_str(), (const uint8_t *)host + i * (nbytes / 3), nbytes / 3));
+    return VSIM_OK;
   }
   auto it = m->slots.find(name);
   if (it == m->slots.end()) { set_error(std::string("set_tensor: unknown tensor ") + name); return VSIM_EINVAL; }
@@ -1442,15 +1347,11 @@ int vsim_model_set_tensor(vsim_model *m, const char *name, const void *host, siz
 
 int vsim_model_get_tensor(vsim_model *m, const char *name, void *host, size_t nbytes) {
   if (!m || !name || !host) { set_error("get_tensor: null argument"); return VSIM_EINVAL; }
-  {  // BLOOM's fused query_key_value weight: the three row blocks back to back
-    const std::string n(name), suf = "attention.query_key_value.weight";
-    if (m->arch == VSIM_ARCH_BLOOM && n.size() >= suf.size() && n.compare(n.size() - suf.size(), suf.size(), suf) == 0) {
-      const char *parts[3] = {"/q", "/k", "/v"};
-      if (nbytes % 3 != 0) { set_error("get_tensor: fused qkv size"); return VSIM_EINVAL; }
-      for (int i = 0; i < 3; ++i)
-        RC(vsim_model_get_tensor(m, (n + parts[i]).c_str(), (uint8_t *)host + i * (nbytes / 3), nbytes / 3));
-      return VSIM_OK;
-    }
+  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks back to back
+    if (nbytes % 3 != 0) { set_error("get_tensor: fused qkv size"); return VSIM_EINVAL; }
+    for (int i = 0; i < 3; ++i)
+      RC(vsim_model_get_tensor(m, (n + QKV_PARTS[i]).c_str(), (uint8_t *)host + i * (nbytes / 3), nbytes / 3));
+    return VSIM_OK;
   }
   auto it = m->slots.find(name);
   if (it == m->slots.end()) { set_error(std::string("get_tensor: unknown tensor ") + name); return VSIM_EINVAL; }
@@ -1646,75 +1547,85 @@ int upload_step(vsim_model *m) {
 
 __global__ void k_npast_advance(int *npast) { npast[0] += 1; }
 
-// One pipeline-stage step from the bound device buffers: token (first stage) or residual
-// (other stages) in, this stage's layers, then the residual out (non-last stages) or the
-// device argmax into the bound token word (last stage), then n_past + 1 on the device.
-int enqueue_stage(vsim_model *m, int &nk) {
+// The whole single-token step of a kind, as decode_graph captures it and the eager paths run it:
+//   STEP_LOGITS  uploads, the decode kernels, then the logits to their pinned host row (last
+//                stage, when wanted) or the residual to resid_out (other stages, when given)
+//   STEP_ARGMAX  uploads, the decode kernels, the device argmax and its 4-byte copy-out
+//   STEP_GEN     no uploads, no copy-out: the argmax feeds the next step (launch_argmax_gen)
+//   STEP_STAGE   from the bound device buffers: token (first stage) or residual (other stages)
+//                in, this stage's layers, then the residual out (non-last stages) or the device
+//                argmax into the bound token word (last stage), then n_past + 1 on the device
+int enqueue_step(vsim_model *m, StepKind kind, int &nk, bool want_logits = true, float *resid_out = nullptr) {
   hipStream_t s = m->stream;
-  const int E = m->hp.n_embd;
-  if (m->first) {
+  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+  if (kind == STEP_STAGE && m->first)
     VSIM_HIP(hipMemcpyAsync(m->tok_dev, m->st_tok_in, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-  } else {
+  else if (kind == STEP_STAGE)
     VSIM_HIP(hipMemcpyAsync(m->inpL, m->st_resid_in, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
-  }
+  else if (kind != STEP_GEN)
+    RC(upload_step(m));
   RC(enqueue_decode(m, nk));
-  if (m->last) {
-    RC(launch_argmax(m->logits, m->hp.n_vocab, m->st_tok_out, m->am_ws, s));
-    ++nk;
-  } else {
-    VSIM_HIP(hipMemcpyAsync(m->st_resid_out, m->resid_final, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
+  switch (kind) {
+    case STEP_LOGITS:
+      if (m->last && want_logits)
+        VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, s));
+      else if (!m->last && resid_out)
+        VSIM_HIP(hipMemcpyAsync(resid_out, m->resid_final, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
+      break;
+    case STEP_ARGMAX:
+      RC(launch_argmax(m->logits, V, m->am_dev, m->am_ws, s));
+      ++nk;
+      VSIM_HIP(hipMemcpyAsync(m->am_host, m->am_dev, sizeof(int), hipMemcpyDeviceToHost, s));
+      break;
+    case STEP_GEN:
+      RC(launch_argmax_gen(m->logits, V, m->am_dev, m->am_ws, m->tok_dev, m->npast_dev, m->hist_dev, s));
+      ++nk;
+      break;
+    case STEP_STAGE:
+      if (m->last) {
+        RC(launch_argmax(m->logits, V, m->st_tok_out, m->am_ws, s));
+        ++nk;
+      } else {
+        VSIM_HIP(hipMemcpyAsync(m->st_resid_out, m->resid_final, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
+      }
+      hipLaunchKernelGGL(k_npast_advance, dim3(1), dim3(1), 0, s, m->npast_dev);
+      VSIM_HIP(hipGetLastError());
+      ++nk;
+      break;
   }
-  hipLaunchKernelGGL(k_npast_advance, dim3(1), dim3(1), 0, s, m->npast_dev);
-  VSIM_HIP(hipGetLastError());
-  ++nk;
   return VSIM_OK;
 }
 
-// Capture (once per mode) the whole single-token step as a hipGraph: uploads, the decode
-// kernels, and either the logits copy-out or the device argmax and its 4-byte copy-out.
-// kind 2: the device-resident greedy loop's step -- no uploads, no copy-out; the argmax
-// feeds the next step (launch_argmax_gen).
-int decode_graph(vsim_model *m, int kind) {
-  const bool argmax = kind == 1, gen = kind == 2, stage = kind == 3;
-  hipGraph_t &graph = stage ? m->graph_st : gen ? m->graph_gen : argmax ? m->graph_am : m->graph;
-  hipGraphExec_t &gexec = stage ? m->gexec_st : gen ? m->gexec_gen : argmax ? m->gexec_am : m->gexec;
-  int &gmode = stage ? m->graph_st_mode : gen ? m->graph_gen_mode : argmax ? m->graph_am_mode : m->graph_mode;
-  if (gexec && gmode == m->mode) return VSIM_OK;
-  if (gexec) (void)hipGraphExecDestroy(gexec);
-  if (graph) (void)hipGraphDestroy(graph);
-  gexec = nullptr;
-  graph = nullptr;
-  hipStream_t s = m->stream;
-  const int V = m->hp.n_vocab;
-  VSIM_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  int gk = 0;
-  int rc = gen || stage ? VSIM_OK : upload_step(m);
-  if (rc == 0 && stage) {
-    rc = enqueue_stage(m, gk);
-  } else if (rc == 0) {
-    rc = enqueue_decode(m, gk);
+// Capture (once per kind and mode) the whole step as a hipGraph.
+int decode_graph(vsim_model *m, StepKind kind) {
+  StepGraph &g = m->step[kind];
+  if (g.exec && g.mode == m->mode) return VSIM_OK;
+  drop(g);
+  VSIM_HIP(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
+  int nk = 0;
+  const int rc = enqueue_step(m, kind, nk);
+  hipGraph_t captured = nullptr;
+  const hipError_t ce = hipStreamEndCapture(m->stream, &captured);
+  if (rc) {
+    if (captured) (void)hipGraphDestroy(captured);
+    return rc;
   }
-  if (rc == 0 && stage) {
-  } else if (rc == 0 && gen) {
-    rc = launch_argmax_gen(m->logits, V, m->am_dev, m->am_ws, m->tok_dev, m->npast_dev, m->hist_dev, s);
-    ++gk;
-  } else if (rc == 0 && argmax) {
-    rc = launch_argmax(m->logits, V, m->am_dev, m->am_ws, s);
-    ++gk;
-    if (rc == 0 && hipMemcpyAsync(m->am_host, m->am_dev, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess)
-      rc = hip_fail(hipErrorUnknown, "capture argmax copy");
-  } else if (rc == 0 &&
-             hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, s) != hipSuccess) {
-    rc = hip_fail(hipErrorUnknown, "capture logits copy");
-  }
-  hipGraph_t g = nullptr;
-  const hipError_t ce = hipStreamEndCapture(s, &g);
-  if (rc) return rc;
   if (ce != hipSuccess) return hip_fail(ce, "hipStreamEndCapture");
-  graph = g;
-  VSIM_HIP(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-  gmode = m->mode;
-  m->graph_kernels_kind[kind] = gk;
+  g.graph = captured;
+  VSIM_HIP(hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0));
+  g.mode = m->mode;
+  g.kernels = nk;
+  return VSIM_OK;
+}
+
+// One step of a kind: its graph replayed (the token / n_past uploads are nodes of the graph:
+// they read the pinned host words when the graph runs), or enqueued eagerly.  Profiling needs
+// the eager form (an event pair around every launch).  nk: the step's kernels, either way.
+int run_step(vsim_model *m, StepKind kind, bool graph, int &nk, bool want_logits = true, float *resid_out = nullptr) {
+  if (!graph || m->profile) return enqueue_step(m, kind, nk, want_logits, resid_out);
+  RC(decode_graph(m, kind));
+  VSIM_HIP(hipGraphLaunch(m->step[kind].exec, m->stream));
+  nk = m->step[kind].kernels;
   return VSIM_OK;
 }
 
@@ -1724,7 +1635,7 @@ extern "C" {
 
 int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *next_token) {
   if (!m || !next_token) { set_error("eval_argmax: null argument"); return VSIM_EINVAL; }
-  if (!m->first || !m->last || !fused_ok(m, 1)) {
+  if (!m->first || !m->last) {
     set_error("eval_argmax: needs a whole-model stage with the single-token decode path");
     return VSIM_EINVAL;
   }
@@ -1732,27 +1643,16 @@ int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *ne
   VSIM_HIP(hipSetDevice(m->device));
   const ErrScope es(m);
   RC(ensure_scratch(m, 1));
-  const int V = m->hp.n_vocab;
-  if (token < 0 || token >= V) { set_error("eval_argmax: token id out of range"); return VSIM_EINVAL; }
+  if (token < 0 || token >= m->hp.n_vocab) { set_error("eval_argmax: token id out of range"); return VSIM_EINVAL; }
   m->tok_host[0] = token;
   m->npast_host[0] = n_past;
   m->prof_npast = n_past;
   m->st_npast = -1;  // this step sets the device n_past: a stage step needs a new stage_begin
-  hipStream_t s = m->stream;
-  if (m->graph_enabled && !m->profile) {
-    RC(decode_graph(m, 1));
-    VSIM_HIP(hipGraphLaunch(m->gexec_am, s));
-    m->kernels_last = m->graph_kernels_kind[1];
-  } else {
-    int nk = 0;
-    RC(upload_step(m));
-    RC(enqueue_decode(m, nk));
-    RC(launch_argmax(m->logits, V, m->am_dev, m->am_ws, s));
-    VSIM_HIP(hipMemcpyAsync(m->am_host, m->am_dev, sizeof(int), hipMemcpyDeviceToHost, s));
-    m->kernels_last = nk + 1;
-  }
+  int nk = 0;
+  RC(run_step(m, STEP_ARGMAX, m->graph_enabled, nk));
+  m->kernels_last = nk;
   RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(s));
+  VSIM_HIP(hipStreamSynchronize(m->stream));
   RC(spin_check(m));
   *next_token = m->am_host[0];
   if (m->profile) RC(prof_collect(m));
@@ -1761,7 +1661,7 @@ int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *ne
 
 int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, int32_t *tokens_out) {
   if (!m || !tokens_out || n_steps < 0) { set_error("generate: bad argument"); return VSIM_EINVAL; }
-  if (!m->first || !m->last || !fused_ok(m, 1)) {
+  if (!m->first || !m->last) {
     set_error("generate: needs a whole-model stage with the single-token decode path");
     return VSIM_EINVAL;
   }
@@ -1774,21 +1674,13 @@ int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, i
   hipStream_t s = m->stream;
   m->tok_host[0] = token;
   m->npast_host[0] = n_past;
-  m->prof_npast = n_past;
   m->st_npast = -1;  // the loop advances the device n_past: a stage step needs a new stage_begin
   RC(upload_step(m));
-  if (m->graph_enabled && !m->profile) {
-    RC(decode_graph(m, 2));
-    for (int i = 0; i < n_steps; ++i) VSIM_HIP(hipGraphLaunch(m->gexec_gen, s));
-    m->kernels_last = m->graph_kernels_kind[2];  // kernels of one decode step (argmax included)
-  } else {
-    for (int i = 0; i < n_steps; ++i) {
-      int nk = 0;
-      m->prof_npast = n_past + i;
-      RC(enqueue_decode(m, nk));
-      RC(launch_argmax_gen(m->logits, m->hp.n_vocab, m->am_dev, m->am_ws, m->tok_dev, m->npast_dev, m->hist_dev, s));
-      m->kernels_last = nk + 1;
-    }
+  for (int i = 0; i < n_steps; ++i) {
+    int nk = 0;
+    m->prof_npast = n_past + i;
+    RC(run_step(m, STEP_GEN, m->graph_enabled, nk));
+    m->kernels_last = nk;  // kernels of one decode step (argmax included)
   }
   VSIM_HIP(hipMemcpyAsync(tokens_out, m->hist_dev + n_past, sizeof(int32_t) * n_steps, hipMemcpyDeviceToHost, s));
   RC(spin_read(m));
@@ -1805,10 +1697,7 @@ int vsim_model_reserve(vsim_model *m, int n_tokens) {
   RC(ensure_scratch(m, n_tokens));
   const int E = E_(m), d = E / m->hp.n_head;
   if (n_tokens >= 8 && attn_prefill_supported(d) && E % 64 == 0) {
-    if (!m->pf_scratch) {
-      m->pf_bytes = attn_prefill_scratch(E, m->n_ctx);
-      VSIM_HIP(hipMalloc(&m->pf_scratch, m->pf_bytes));
-    }
+    RC(ensure_pf_scratch(m));
     RC(attn_prefill_prepare());
   }
   if (n_tokens >= G2_MIN_N) RC(gemm_reserve_stream(m->stream));
@@ -1827,7 +1716,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   int nk = 0;
-  if (fused_ok(m, N)) {
+  if (N == 1) {  // every graph has a single-token step (the serial-residual ones with 6 launches per layer)
     if (m->first) {
       if (!tokens) { set_error("eval: first stage needs tokens"); return VSIM_EINVAL; }
       if (tokens[0] < 0 || tokens[0] >= V) { set_error("eval: token id out of range"); return VSIM_EINVAL; }
@@ -1837,24 +1726,11 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
       VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
     }
     m->npast_host[0] = n_past;
-  m->prof_npast = n_past;
-    const bool use_graph = m->graph_enabled && m->first && m->last && !m->profile;
-    if (use_graph) {
-      // the token / n_past uploads are nodes of the graph (they read the pinned host words
-      // when the graph runs)
-      RC(decode_graph(m, 0));
-      VSIM_HIP(hipGraphLaunch(m->gexec, s));
-      nk = m->graph_kernels_kind[0];
-    } else {
-      RC(upload_step(m));
-      RC(enqueue_decode(m, nk));
-      if (m->last && logits)
-        VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, s));
-      else if (!m->last && resid_out)
-        VSIM_HIP(hipMemcpyAsync(resid_out, m->resid_final, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
-    }
+    m->prof_npast = n_past;
+    // (the graph is the whole model's step: a partial stage, with its residual in and out, runs eagerly)
+    RC(run_step(m, STEP_LOGITS, m->graph_enabled && m->first && m->last, nk, logits != nullptr, resid_out));
   } else {
-    // general path: prompt batches (N > 1) and the serial-residual GPT-NeoX variant
+    // general path: prompt batches (N > 1)
     if (m->first) {
       if (!tokens) { set_error("eval: first stage needs tokens"); return VSIM_EINVAL; }
       for (int i = 0; i < N; ++i) {
@@ -1903,17 +1779,11 @@ int vsim_model_stage_bind(vsim_model *m, const int32_t *tok_in, const float *res
     set_error("stage_bind: first stage needs tok_in, later stages resid_in, the last tok_out, the others resid_out");
     return VSIM_EINVAL;
   }
-  if (!fused_ok(m, 1)) { set_error("stage_bind: needs the single-token decode path"); return VSIM_EINVAL; }
   VSIM_HIP(hipSetDevice(m->device));
   RC(ensure_scratch(m, 1));
-  if (m->st_tok_in != tok_in || m->st_resid_in != resid_in || m->st_resid_out != resid_out || m->st_tok_out != tok_out) {
-    // the captured step reads the bound addresses: recapture on the next step
-    if (m->gexec_st) (void)hipGraphExecDestroy(m->gexec_st);
-    if (m->graph_st) (void)hipGraphDestroy(m->graph_st);
-    m->gexec_st = nullptr;
-    m->graph_st = nullptr;
-    m->graph_st_mode = -1;
-  }
+  // the captured step reads the bound addresses: recapture on the next step
+  if (m->st_tok_in != tok_in || m->st_resid_in != resid_in || m->st_resid_out != resid_out || m->st_tok_out != tok_out)
+    drop(m->step[STEP_STAGE]);
   m->st_tok_in = tok_in;
   m->st_resid_in = resid_in;
   m->st_resid_out = resid_out;
@@ -1939,15 +1809,9 @@ int vsim_model_stage_step(vsim_model *m) {
   VSIM_HIP(hipSetDevice(m->device));
   const ErrScope es(m);
   m->prof_npast = m->st_npast;
-  if (m->graph_enabled && !m->profile) {
-    RC(decode_graph(m, 3));
-    VSIM_HIP(hipGraphLaunch(m->gexec_st, m->stream));
-    m->kernels_last = m->graph_kernels_kind[3];
-  } else {
-    int nk = 0;
-    RC(enqueue_stage(m, nk));
-    m->kernels_last = nk;
-  }
+  int nk = 0;
+  RC(run_step(m, STEP_STAGE, m->graph_enabled, nk));
+  m->kernels_last = nk;
   m->st_npast++;
   if (m->profile) {
     RC(spin_read(m));
@@ -1962,26 +1826,18 @@ int vsim_model_debug_poison(vsim_model *m, int n_tokens) {
   if (!m || n_tokens <= 0) { set_error("debug_poison: bad argument"); return VSIM_EINVAL; }
   VSIM_HIP(hipSetDevice(m->device));
   RC(ensure_scratch(m, n_tokens));
-  const int E = m->hp.n_embd;
-  if (!m->pf_scratch) {
-    m->pf_bytes = attn_prefill_scratch(E, m->n_ctx);
-    VSIM_HIP(hipMalloc(&m->pf_scratch, m->pf_bytes));
-  }
-  const size_t n = m->n_max, F = 4 * (size_t)E, V = m->hp.n_vocab, H = m->hp.n_head;
-  const size_t nl = (size_t)std::max(1, m->l1 - m->l0);
-  struct Buf {
-    void *p;
-    size_t bytes;
-  } bufs[] = {
-      {m->inpL, n * E * 4}, {m->cur1, n * E * 4}, {m->cur2, n * E * 4}, {m->Qb, n * E * 4}, {m->Kb, n * E * 4},
-      {m->Vb, n * E * 4}, {m->attn_in, n * E * 4}, {m->attn, n * E * 4}, {m->ff, n * E * 4}, {m->fch, n * F * 4},
-      {m->kq, n * H * m->n_ctx * 4}, {m->logits, V * 4}, {m->xq1, n * E / QK * QBYTES},
-      {m->xq2, n * E / QK * QBYTES}, {m->xq3, n * F / QK * QBYTES}, {m->xd1, n * E * 4}, {m->xd2, n * E * 4},
-      {m->xd3, n * F * 4}, {m->xqa, n * E / QK * QBYTES}, {m->xda, n * E * 4}, {m->inpL2, (size_t)E * 4},
-      {m->pf_scratch, m->pf_bytes & ~(size_t)3}, {m->pf_x16, n >= (size_t)GEMM_MIN_N ? n * (E + F) * 2 : 0},
-      {m->kcache, nl * m->n_ctx * E * 4}, {m->vcache, nl * m->n_ctx * E * 4}};
-  for (const Buf &b : bufs)
-    if (b.p && b.bytes) VSIM_HIP(hipMemsetD32Async((hipDeviceptr_t)b.p, 0x7FC00000u, b.bytes / 4, m->stream));
+  RC(ensure_pf_scratch(m));
+  auto nan_fill = [&](void *p, size_t bytes) -> int {
+    if (p && bytes) VSIM_HIP(hipMemsetD32Async((hipDeviceptr_t)p, 0x7FC00000u, bytes / 4, m->stream));
+    return VSIM_OK;
+  };
+  for (const ScratchBuf &b : scratch_table(m, m->n_max))
+    if (b.flags & S_POISON) RC(nan_fill(*b.p, b.bytes));
+  // ... and what the scratch table does not own
+  const size_t kv = (size_t)std::max(1, m->l1 - m->l0) * m->n_ctx * E_(m) * sizeof(float);
+  RC(nan_fill(m->pf_scratch, m->pf_bytes & ~(size_t)3));
+  RC(nan_fill(m->kcache, kv));
+  RC(nan_fill(m->vcache, kv));
   VSIM_HIP(hipStreamSynchronize(m->stream));
   return VSIM_OK;
 }
