@@ -14,7 +14,10 @@
  *     (reference-bit-identical) or fast numeric mode.  Used by the parity tests.
  *  3. Model-level executor (vsim_model_*): device-resident GPT-NeoX (vsim.cpp:470-747)
  *     and GPT-J graphs, whole decode step captured in a hipGraph; host<->device traffic
- *     per token is the token ids in and one logits row out (vsim.cpp:736-737).
+ *     per token is the token ids in and one logits row out (vsim.cpp:736-737), or, for the
+ *     greedy and the sampled step, a token id or at most 64 (value, id) candidates out.
+ *  plus the sampler object (vsim_sampler_*): the reference's sampler with its O(n_vocab)
+ *     stage on the device.
  *
  * Device weight layout ("W4T32"): a Q4_0 matrix of M rows x K weights keeps the
  * reference's 0.625 B/weight but splits the 20-byte blocks (ggml.c:204-251) into a
@@ -190,6 +193,25 @@ int vsim_op_gelu(const float *x, float *y, int n, void *stream);
  * std::partial_sort over (logit, id) pairs, whose order among equal keys the standard leaves
  * unspecified; this kernel returns the first index, as numpy does.  Distinct maxima agree. */
 int vsim_op_argmax(const float *x, int n, int32_t *out, void *stream);
+/* The O(n) stage of the reference's sampler (sample_top_p_top_k_repeat_penalty, utils.cpp:339-371:
+ * repetition penalty, temperature scale, top-k) on the device, one launch (k_sample_topk):
+ *   candidate c[i] = (double)x[i] * scale                          id i not in win[0:nw]
+ *                    x[i] < 0 ? c[i] * repeat_penalty : c[i] / repeat_penalty   id i in win
+ * in double and in that order (scale = 1.0 / temp); val[0:k], id[0:k] = the k largest candidates
+ * in descending order.  x, win, val, id are device pointers (x any 4-byte alignment; win may hold
+ * duplicates and ids outside [0, n), which match nothing); enqueued on stream, not synchronized.
+ * Limits: 1 <= k <= min(n, VSIM_TOPK_MAX), 0 <= nw <= VSIM_WINDOW_MAX, else VSIM_EINVAL.
+ * Ties: equal candidates (-0.0 == +0.0) are ordered by the lower id first, inside the list and at
+ * the k-th boundary.  The reference's std::partial_sort over (value, id) pairs leaves the order
+ * of equal values unspecified; distinct values agree with it exactly.  With a NaN logit the
+ * reference's order is undefined and so is this one (the kernel still terminates and writes k
+ * distinct ids of [0, n)).  val holds the candidates' own bits (a -0.0 stays -0.0).
+ * The workspace is the library's, one per (device, stream), zero between launches: calls on one
+ * stream may follow each other without a synchronize. */
+#define VSIM_TOPK_MAX 64
+#define VSIM_WINDOW_MAX 1024
+int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale, double repeat_penalty, int k,
+                 double *val, int32_t *id, void *stream);
 /* scale -> diag_mask_inf(n_past) -> soft_max over p[nz][nr][nc], in place */
 int vsim_op_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, void *stream);
 /* style 0 = GPT-NeoX rotate-half (ggml.c:6086), 1 = GPT-J pairs (ggml.c:5919);
@@ -245,6 +267,39 @@ int vsim_op_norm_f16q(const float *x, int k, int rows, const float *w, const flo
 /* device fp16 tables (exp, gelu) as built by ggml_init (ggml.c:1240-1251) */
 int vsim_op_tables(uint16_t *exp_f16_host, uint16_t *gelu_f16_host);
 
+/* ------------------------------------------------------------- sampler (host) ------ */
+/* The reference's sampler (utils.cpp:339-422) and the last-n window of its main loop
+ * (vsim.cpp:875-876) as an object.  Its work is split in two stages:
+ *   candidates  penalty, temperature and the ordered top-k of the n_vocab logits: on the device
+ *               (vsim_op_topk; the model's sampled step below), or on the host (sample_host);
+ *   finish      on at most top_k candidates, always on the host: p = exp(c - max) in double,
+ *               normalise, the top-p cut and rescale, std::discrete_distribution<> over the
+ *               sampler's std::mt19937.  It stays on the host because its exp is glibc's double
+ *               exp, which the device's does not reproduce bit for bit, and the sampled streams
+ *               are the reference's only if every probability is.
+ * The float parameters widen as the reference's do (top_p, temp, repeat_penalty: float to double;
+ * top_k through (int)(float); the top-p test is top_p < 1.0f).  The window starts as
+ * repeat_last_n zeros, so id 0 is penalised from the first token, as in the reference;
+ * repeat_last_n = 0 means no window.  No function here needs a GPU. */
+typedef struct vsim_sampler vsim_sampler;
+typedef struct {
+  int32_t seed, top_k, repeat_last_n;
+  float top_p, temp, repeat_penalty;
+} vsim_sample_params;
+int vsim_sampler_create(const vsim_sample_params *p, vsim_sampler **out);
+/* a token enters the window without being sampled (the prompt's): drop the oldest, append */
+int vsim_sampler_accept(vsim_sampler *s, int32_t token);
+/* finish on an ordered candidate list (val descending, 1 <= k <= VSIM_TOPK_MAX, else
+ * VSIM_EINVAL): the token drawn, which also enters the window.  One candidate, or a top-p cut
+ * down to one, draws nothing from the generator (libstdc++), and later draws depend on that. */
+int vsim_sampler_pick(vsim_sampler *s, const double *val, const int32_t *id, int k, int32_t *token);
+/* both stages on the host from a logits row, the reference's code as it stands (any top_k in
+ * 1..n; the order of equal candidates is std::partial_sort's); the token enters the window */
+int vsim_sampler_sample_host(vsim_sampler *s, const float *logits, int n, int32_t *token);
+/* tokens drawn by vsim_sampler_pick (the device made the candidates) and by sample_host */
+int vsim_sampler_stats(const vsim_sampler *s, uint64_t *picks, uint64_t *host_picks);
+void vsim_sampler_free(vsim_sampler *s);
+
 /* ------------------------------------------------------ 3. model-level executor ---- */
 typedef struct vsim_model vsim_model;
 
@@ -290,6 +345,22 @@ int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *ne
  * n_steps generated tokens are copied to tokens_out at the end.  Same tokens as calling
  * vsim_model_eval_argmax n_steps times. */
 int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, int32_t *tokens_out);
+/* Sampled single-token decode step of a whole-model stage: eval of `token` at n_past, then the
+ * candidate stage of sampler s on the device logits (k_sample_topk, inside the step's hipGraph;
+ * the window, k, scale and penalty are uploaded per step, so samplers may alternate on one
+ * model), one copy of at most VSIM_TOPK_MAX (value, id) pairs to the host, and
+ * vsim_sampler_pick there.  The logits row never leaves the device.  The same tokens as
+ * vsim_model_eval + vsim_sampler_sample_host wherever the candidates are distinct (ties:
+ * vsim_op_topk).  A sampler outside the device stage's limits -- top_k > VSIM_TOPK_MAX or
+ * > n_vocab, repeat_last_n > VSIM_WINDOW_MAX, temp <= 0 or repeat_penalty <= 0 -- takes exactly
+ * that host path instead; vsim_sampler_stats tells which ran. */
+int vsim_model_eval_sample(vsim_model *m, vsim_sampler *s, int n_past, int32_t token, int32_t *next_token);
+/* The loop over vsim_model_eval_sample: up to n_steps tokens from (n_past, token) into
+ * tokens_out, *n_out of them; stops after a step that produced `eos` (-1: none), as the
+ * reference's loop does for id 2 (vsim.cpp:894).  One host round trip per token (the finish
+ * stage): a sampled loop without it would need the device's exp to be glibc's. */
+int vsim_model_generate_sampled(vsim_model *m, vsim_sampler *s, int n_past, int32_t token, int n_steps, int32_t eos,
+                                int32_t *tokens_out, int *n_out);
 /* Pipeline stage step: the single-token step of this stage's layers between
  * device buffers the caller binds once -- tok_in (first stage: the token to embed), resid_in
  * (other stages: the [n_embd] residual from the previous stage), resid_out (non-last stages:

@@ -140,6 +140,25 @@ int vsim_op_argmax(const float *x, int n, int32_t *out, void *stream) {
   }
   return launch_argmax(x, n, (int *)out, ws, (hipStream_t)stream);
 }
+int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale, double repeat_penalty, int k,
+                 double *val, int32_t *id, void *stream) {
+  // one workspace per (device, stream), kept, as vsim_op_argmax's: the kernel leaves its counter zero
+  static std::mutex mu;
+  static std::map<std::pair<int, void *>, void *> wss;
+  int dev = 0;
+  VSIM_HIP(hipGetDevice(&dev));
+  void *ws = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    void *&w = wss[{dev, stream}];
+    if (!w) {
+      VSIM_HIP(hipMalloc(&w, TOPK_WS_BYTES));
+      VSIM_HIP(hipMemset(w, 0, TOPK_WS_BYTES));
+    }
+    ws = w;
+  }
+  return launch_topk(x, n, nullptr, win, nw, scale, repeat_penalty, k, val, id, ws, (hipStream_t)stream);
+}
 int vsim_op_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, void *stream) {
   return launch_attn_softmax(p, nc, nr, nz, n_past, scale, (hipStream_t)stream);
 }

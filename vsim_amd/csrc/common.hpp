@@ -306,6 +306,24 @@ int launch_norm(const float *x, float *y, int k, int rows, const float *w, const
 int launch_norm_f16q(const float *x, void *x16, int k, int rows, const float *w, const float *b, hipStream_t s);
 // ws: 16 bytes of zeroed device memory per concurrent caller (the kernel leaves it zeroed)
 int launch_argmax(const float *x, int n, int *out, unsigned long long *ws, hipStream_t s);
+// The sampler's device stage (sample.hip, vsim_op_topk): repetition penalty, temperature scale
+// and the ordered top-k of a logit row.  pb non-null: k, nw, scale, penalty and the window are
+// read from that device block when the kernel runs (the model's captured step: nothing of a
+// sampler is baked into the graph) and the win .. k arguments are ignored.  ws: TOPK_WS_BYTES
+// of device memory per concurrent caller whose first word is zero (the kernel leaves it zero).
+struct TopkParams {
+  double scale, penalty;
+  int32_t k, nw;
+  int32_t win[VSIM_WINDOW_MAX];
+};
+struct TopkOut {
+  double val[VSIM_TOPK_MAX];
+  int32_t id[VSIM_TOPK_MAX];
+};
+constexpr int TOPK_MAX_WG = 64;
+constexpr size_t TOPK_WS_BYTES = 256 + (size_t)TOPK_MAX_WG * 64 * (sizeof(unsigned long long) + sizeof(uint32_t));
+int launch_topk(const float *x, int n, const TopkParams *pb, const int32_t *win, int nw, double scale, double penalty,
+                int k, double *val, int32_t *id, void *ws, hipStream_t s);
 int launch_gemm_q4_f16(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
 // fast-mode prompt batches (n >= GEMM_MIN_N): activation rows quantized (optionally after
 // bias + GELU) straight to the GEMM's fp16 operand x16 [n][K], and the GEMM on it

@@ -9,8 +9,8 @@
 //
 // What the host side keeps is described once each: the tensors of an architecture
 // (arch_table: plan_slots and bind_pointers walk it), the scratch buffers (scratch_table:
-// allocated, freed and poisoned from it), the four single-token step graphs (StepGraph
-// step[4], captured by decode_graph) and what a step of each kind enqueues (enqueue_step:
+// allocated, freed and poisoned from it), the five single-token step graphs (StepGraph
+// step[5], captured by decode_graph) and what a step of each kind enqueues (enqueue_step:
 // the captured and the eager form are the same call).  LAUNCH brackets a profiled launch.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "fast.hpp"
+#include "sampler.hpp"
 #include "../../include/vsim_hip.h"
 
 using namespace vsim;
@@ -55,7 +56,10 @@ struct LayerW {
 //                the argmax kernel feeds tok_dev / npast_dev and records into hist_dev[n_ctx]
 //   STEP_STAGE   the pipeline stage step (vsim_model_stage_*) between the bound device buffers,
 //                ending by advancing n_past on the device
-enum StepKind { STEP_LOGITS = 0, STEP_ARGMAX = 1, STEP_GEN = 2, STEP_STAGE = 3 };
+//   STEP_SAMPLE  the sampled variant (vsim_model_eval_sample): the sampler's parameter block and
+//                window are uploaded too, k_sample_topk follows the decode kernels, and the
+//                candidates (TopkOut, 768 bytes) are copied out instead of the logits
+enum StepKind { STEP_LOGITS = 0, STEP_ARGMAX = 1, STEP_GEN = 2, STEP_STAGE = 3, STEP_SAMPLE = 4 };
 struct StepGraph {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
@@ -105,10 +109,15 @@ struct vsim_model {
   float *inpL2 = nullptr;     // second residual buffer (the join alternates between the two)
   float *resid_final = nullptr;  // where the last fused step left the stage's residual
   int *npast_dev = nullptr, *npast_host = nullptr;
-  StepGraph step[4];  // by StepKind
+  StepGraph step[5];  // by StepKind
   int *am_dev = nullptr, *am_host = nullptr;  // the greedy steps' token
   unsigned long long *am_ws = nullptr;  // the argmax's key and workgroup count (zero between launches)
   int *hist_dev = nullptr;              // STEP_GEN's record [n_ctx]
+  // STEP_SAMPLE: the sampler's parameter block (pinned, device), the candidates (device, pinned)
+  // and k_sample_topk's workspace (its counter zero between launches)
+  TopkParams *sp_host = nullptr, *sp_dev = nullptr;
+  TopkOut *so_dev = nullptr, *so_host = nullptr;
+  void *tk_ws = nullptr;
   // pipeline stage step (vsim_model_stage_*): device buffers the caller binds (the token in
   // on the first stage, the residual in / out between stages, the greedy token out on the
   // last) and the host's count of enqueued steps (n_ctx bound)
@@ -220,6 +229,11 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->am_ws, 2 * sizeof(unsigned long long), S_ZERO);
   add(&m->am_host, sizeof(int), S_PINNED);
   add(&m->hist_dev, (size_t)m->n_ctx * sizeof(int));
+  add(&m->sp_host, sizeof(TopkParams), S_PINNED);
+  add(&m->sp_dev, sizeof(TopkParams));
+  add(&m->so_dev, sizeof(TopkOut));
+  add(&m->so_host, sizeof(TopkOut), S_PINNED);
+  add(&m->tk_ws, TOPK_WS_BYTES, S_ZERO);
   add(&m->tail_done, ncnt * sizeof(unsigned), S_ZERO);
   add(&m->lnt_ep, lnt_bytes(E), S_ZERO);  // one allocation, carved by carve_lnt
   add(&m->fast_ffp, 8 * E * f);
@@ -458,6 +472,7 @@ int spin_check(vsim_model *m) {
     add_model_spin_timeouts(grew);
     // a workgroup that gave up may have left the argmax workspace mid-update: zero it again
     (void)hipMemsetAsync(m->am_ws, 0, 2 * sizeof(unsigned long long), m->stream);
+    (void)hipMemsetAsync(m->tk_ws, 0, sizeof(unsigned), m->stream);
     (void)hipStreamSynchronize(m->stream);
     set_error("a bounded cross-workgroup wait gave up " + std::to_string(grew) +
               " time(s) in this call (device " + std::to_string(m->device) + "): results not valid");
@@ -1555,6 +1570,8 @@ __global__ void k_npast_advance(int *npast) { npast[0] += 1; }
 //   STEP_STAGE   from the bound device buffers: token (first stage) or residual (other stages)
 //                in, this stage's layers, then the residual out (non-last stages) or the device
 //                argmax into the bound token word (last stage), then n_past + 1 on the device
+//   STEP_SAMPLE  uploads (the sampler's block too), the decode kernels, k_sample_topk reading its
+//                k, window, scale and penalty from that block, and the candidates' copy-out
 int enqueue_step(vsim_model *m, StepKind kind, int &nk, bool want_logits = true, float *resid_out = nullptr) {
   hipStream_t s = m->stream;
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
@@ -1564,6 +1581,8 @@ int enqueue_step(vsim_model *m, StepKind kind, int &nk, bool want_logits = true,
     VSIM_HIP(hipMemcpyAsync(m->inpL, m->st_resid_in, sizeof(float) * E, hipMemcpyDeviceToDevice, s));
   else if (kind != STEP_GEN)
     RC(upload_step(m));
+  if (kind == STEP_SAMPLE)
+    VSIM_HIP(hipMemcpyAsync(m->sp_dev, m->sp_host, sizeof(TopkParams), hipMemcpyHostToDevice, s));
   RC(enqueue_decode(m, nk));
   switch (kind) {
     case STEP_LOGITS:
@@ -1580,6 +1599,12 @@ int enqueue_step(vsim_model *m, StepKind kind, int &nk, bool want_logits = true,
     case STEP_GEN:
       RC(launch_argmax_gen(m->logits, V, m->am_dev, m->am_ws, m->tok_dev, m->npast_dev, m->hist_dev, s));
       ++nk;
+      break;
+    case STEP_SAMPLE:
+      LAUNCH(m, nk,
+             launch_topk(m->logits, V, m->sp_dev, nullptr, 0, 0.0, 0.0, 0, m->so_dev->val, m->so_dev->id, m->tk_ws, s),
+             "k_sample_topk", (double)V * sizeof(float));
+      VSIM_HIP(hipMemcpyAsync(m->so_host, m->so_dev, sizeof(TopkOut), hipMemcpyDeviceToHost, s));
       break;
     case STEP_STAGE:
       if (m->last) {
@@ -1687,6 +1712,64 @@ int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, i
   VSIM_HIP(hipStreamSynchronize(s));
   RC(spin_check(m));
   if (m->profile) RC(prof_collect(m));
+  return VSIM_OK;
+}
+
+int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t token, int32_t *next_token) {
+  if (!m || !sm || !next_token) { set_error("eval_sample: null argument"); return VSIM_EINVAL; }
+  if (!m->first || !m->last) {
+    set_error("eval_sample: needs a whole-model stage with the single-token decode path");
+    return VSIM_EINVAL;
+  }
+  if (n_past < 0 || n_past + 1 > m->n_ctx) { set_error("eval_sample: n_past + 1 exceeds n_ctx"); return VSIM_EINVAL; }
+  const int V = m->hp.n_vocab;
+  if (token < 0 || token >= V) { set_error("eval_sample: token id out of range"); return VSIM_EINVAL; }
+  // outside the device stage's limits: the logits step and the reference's host code
+  if (sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX || !(sm->temp > 0.0) ||
+      !(sm->repeat_penalty > 0.0)) {
+    std::vector<float> lg((size_t)V);
+    RC(vsim_model_eval(m, n_past, &token, 1, nullptr, nullptr, lg.data()));
+    return vsim_sampler_sample_host(sm, lg.data(), V, next_token);
+  }
+  if (sm->top_k < 1) { set_error("eval_sample: top_k < 1"); return VSIM_EINVAL; }
+  VSIM_HIP(hipSetDevice(m->device));
+  const ErrScope es(m);
+  RC(ensure_scratch(m, 1));
+  m->tok_host[0] = token;
+  m->npast_host[0] = n_past;
+  m->prof_npast = n_past;
+  m->st_npast = -1;  // this step sets the device n_past: a stage step needs a new stage_begin
+  TopkParams *pb = m->sp_host;
+  pb->scale = 1.0 / sm->temp;
+  pb->penalty = sm->repeat_penalty;
+  pb->k = sm->top_k;
+  pb->nw = (int32_t)sm->win.size();
+  if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
+  int nk = 0;
+  RC(run_step(m, STEP_SAMPLE, m->graph_enabled, nk));
+  m->kernels_last = nk;
+  RC(spin_read(m));
+  VSIM_HIP(hipStreamSynchronize(m->stream));
+  RC(spin_check(m));
+  if (m->profile) RC(prof_collect(m));
+  return vsim_sampler_pick(sm, m->so_host->val, m->so_host->id, sm->top_k, next_token);
+}
+
+int vsim_model_generate_sampled(vsim_model *m, vsim_sampler *sm, int n_past, int32_t token, int n_steps, int32_t eos,
+                                int32_t *tokens_out, int *n_out) {
+  if (!m || !sm || !tokens_out || !n_out || n_steps < 0) { set_error("generate_sampled: bad argument"); return VSIM_EINVAL; }
+  *n_out = 0;
+  if (n_past < 0 || n_past + n_steps > m->n_ctx) {
+    set_error("generate_sampled: n_past + n_steps exceeds n_ctx");
+    return VSIM_EINVAL;
+  }
+  for (int i = 0; i < n_steps; ++i) {
+    int32_t nxt = 0;
+    RC(vsim_model_eval_sample(m, sm, n_past + i, token, &nxt));
+    tokens_out[(*n_out)++] = nxt;
+    if (nxt == eos) break;
+    token = nxt;
+  }
   return VSIM_OK;
 }
 

@@ -44,7 +44,12 @@ EXPORTS = [
     "vsim_graph_set_profile", "vsim_graph_profile_report", "vsim_graph_match", "vsim_graph_fast_stats",
     "vsim_model_stage_bind", "vsim_model_stage_begin", "vsim_model_stage_step", "vsim_model_sync",
     "vsim_model_debug_poison",
+    "vsim_op_topk", "vsim_sampler_create", "vsim_sampler_accept", "vsim_sampler_pick", "vsim_sampler_sample_host",
+    "vsim_sampler_stats", "vsim_sampler_free", "vsim_model_eval_sample", "vsim_model_generate_sampled",
 ]
+
+TOPK_MAX = 64      # VSIM_TOPK_MAX
+WINDOW_MAX = 1024  # VSIM_WINDOW_MAX
 
 _lib = None
 
@@ -88,6 +93,11 @@ def ggml_f32(buf, ne, nb=None, typ=GGML_TYPE_F32):
         t.nb[i] = nb[i]
     t.data = buf.ctypes.data
     return t
+
+
+class SampleParams(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_int32), ("top_k", ctypes.c_int32), ("repeat_last_n", ctypes.c_int32),
+                ("top_p", ctypes.c_float), ("temp", ctypes.c_float), ("repeat_penalty", ctypes.c_float)]
 
 
 class HParams(ctypes.Structure):
@@ -177,6 +187,18 @@ def lib():
     L.vsim_graph_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * 4
     L.vsim_graph_set_profile.argtypes = [ci]
     L.vsim_graph_profile_report.argtypes = [ctypes.c_char_p, sz]
+    cd, i32p = ctypes.c_double, ctypes.POINTER(ctypes.c_int32)
+    L.vsim_op_topk.argtypes = [vp, ci, vp, ci, cd, cd, ci, vp, vp, vp]
+    L.vsim_sampler_create.argtypes = [ctypes.POINTER(SampleParams), ctypes.POINTER(vp)]
+    L.vsim_sampler_accept.argtypes = [vp, ctypes.c_int32]
+    L.vsim_sampler_pick.argtypes = [vp, vp, vp, ci, i32p]
+    L.vsim_sampler_sample_host.argtypes = [vp, vp, ci, i32p]
+    L.vsim_sampler_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.vsim_sampler_free.restype = None
+    L.vsim_sampler_free.argtypes = [vp]
+    L.vsim_model_eval_sample.argtypes = [vp, vp, ci, ctypes.c_int32, i32p]
+    L.vsim_model_generate_sampled.argtypes = [vp, vp, ci, ctypes.c_int32, ci, ctypes.c_int32, i32p,
+                                              ctypes.POINTER(ci)]
     _lib = L
     return L
 
@@ -198,6 +220,63 @@ def ptr(t) -> int:
 
 def q4_bytes(rows: int, k: int) -> int:
     return int(lib().vsim_q4_bytes(rows, k))
+
+
+class Sampler:
+    """The reference's sampler as an object (vsim_sampler_* in include/vsim_hip.h): the last-n
+    window, the generator, and the k-element finishing stage.  Host code: needs no GPU."""
+
+    def __init__(self, seed=42, top_k=40, top_p=0.95, temp=0.8, repeat_last_n=64, repeat_penalty=1.3):
+        self.h = ctypes.c_void_p()
+        p = SampleParams(seed, top_k, repeat_last_n, top_p, temp, repeat_penalty)
+        check(lib().vsim_sampler_create(ctypes.byref(p), ctypes.byref(self.h)), "sampler_create")
+
+    def accept(self, token: int):
+        """A token that was not sampled (the prompt's) enters the window."""
+        check(lib().vsim_sampler_accept(self.h, int(token)), "sampler_accept")
+
+    def pick(self, val, ids) -> int:
+        """The finishing stage on an ordered candidate list (e.g. topk()'s); the token drawn."""
+        v = np.ascontiguousarray(val, np.float64)
+        i = np.ascontiguousarray(ids, np.int32)
+        tok = ctypes.c_int32()
+        check(lib().vsim_sampler_pick(self.h, ptr(v), ptr(i), int(v.size), ctypes.byref(tok)), "sampler_pick")
+        return tok.value
+
+    def sample_host(self, logits) -> int:
+        """Both stages on the host from a logits row (the reference's code as it stands)."""
+        lg = np.ascontiguousarray(logits, np.float32)
+        tok = ctypes.c_int32()
+        check(lib().vsim_sampler_sample_host(self.h, ptr(lg), int(lg.size), ctypes.byref(tok)), "sample_host")
+        return tok.value
+
+    def stats(self) -> dict:
+        """Tokens drawn so far: by pick (device candidates) and by sample_host."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        check(lib().vsim_sampler_stats(self.h, ctypes.byref(a), ctypes.byref(b)), "sampler_stats")
+        return {"device": a.value, "host": b.value}
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().vsim_sampler_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def topk(x, n, win, scale, repeat_penalty, k, val, ids, stream=None):
+    """vsim_op_topk on device buffers (torch tensors or raw addresses): x float32 [n] (an int
+    address allows any 4-byte alignment), win int32 ids or None, val float64 [k], ids int32 [k].
+    Enqueued on `stream` (a raw hipStream_t, None = the default stream), not synchronized."""
+    def addr(t):
+        return t if isinstance(t, int) or t is None else ptr(t)
+    nw = 0 if win is None else int(win.numel() if hasattr(win, "numel") else win.size)
+    check(lib().vsim_op_topk(addr(x), n, addr(win) if nw else None, nw, float(scale), float(repeat_penalty), k,
+                             addr(val), addr(ids), stream), "topk")
 
 
 class Model:
@@ -269,6 +348,20 @@ class Model:
         out = (ctypes.c_int32 * max(n_steps, 1))()
         check(lib().vsim_model_generate(self.h, n_past, int(token), n_steps, out), "generate")
         return list(out[:n_steps])
+
+    def eval_sample(self, sampler: Sampler, n_past, token) -> int:
+        """Sampled decode step: top-k of the penalised logits on the device, the draw on the host."""
+        nxt = ctypes.c_int32()
+        check(lib().vsim_model_eval_sample(self.h, sampler.h, n_past, int(token), ctypes.byref(nxt)), "eval_sample")
+        return nxt.value
+
+    def generate_sampled(self, sampler: Sampler, n_past, token, n_steps, eos=-1) -> list:
+        """Up to n_steps sampled decode steps; stops after a step that produced `eos`."""
+        out = (ctypes.c_int32 * max(n_steps, 1))()
+        n = ctypes.c_int()
+        check(lib().vsim_model_generate_sampled(self.h, sampler.h, n_past, int(token), n_steps, eos, out,
+                                                ctypes.byref(n)), "generate_sampled")
+        return list(out[:n.value])
 
     def info(self):
         k, g, w = ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()

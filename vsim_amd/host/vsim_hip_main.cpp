@@ -5,15 +5,15 @@
 // cformers/interface.py can spawn it unchanged: banner lines, "<|BEGIN> ", " %d " per id
 // (prompt echoed in n_batch+1 chunks, then sampled ids), " <END|>"; --return_logits
 // prints "logits: %.8f ..." rows.  The model runs in libvsim_hip.so (device resident);
-// this file is host control only.  Extra flags: --device N, --mode exact|fast,
-// --n_ctx N (reference: fixed 512, vsim.cpp:758), --no-graph.
+// this file is host control only: the sampler too is the library's (vsim_sampler_*).
+// Extra flags: --device N, --mode exact|fast, --n_ctx N (reference: fixed 512,
+// vsim.cpp:758), --no-graph, --sampler host|device.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <random>
 #include <string>
 #include <thread>
 #include <vector>
@@ -39,6 +39,7 @@ struct Params {
   int mode = VSIM_MODE_EXACT;
   int n_ctx = 512;
   bool graph = true;
+  bool device_sampler = true;
 };
 
 void usage(const char *argv0, const Params &p) {
@@ -57,6 +58,8 @@ void usage(const char *argv0, const Params &p) {
   fprintf(stderr, "  --mode exact|fast     exact = bit-identical to the reference (default)\n");
   fprintf(stderr, "  --n_ctx N             context length (default 512, as the reference)\n");
   fprintf(stderr, "  --no-graph            launch every kernel eagerly\n");
+  fprintf(stderr, "  --sampler host|device device = penalty, temperature and top-k on the GPU (default);\n");
+  fprintf(stderr, "                        host = the logits row is copied out and sampled on the CPU\n");
 }
 
 // utils.cpp:12-51 (argv[1] is the model type and is skipped)
@@ -86,6 +89,14 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "--mode") p.mode = std::string(next()) == "fast" ? VSIM_MODE_FAST : VSIM_MODE_EXACT;
     else if (a == "--n_ctx") p.n_ctx = std::stoi(next());
     else if (a == "--no-graph") p.graph = false;
+    else if (a == "--sampler") {
+      const std::string v = next();
+      if (v != "host" && v != "device") {
+        fprintf(stderr, "error: --sampler takes host or device\n");
+        exit(1);
+      }
+      p.device_sampler = v == "device";
+    }
     else if (a == "-h" || a == "--help") { usage(argv[0], p); exit(0); }
     else {
       fprintf(stderr, "error: unknown argument: %s\n", a.c_str());
@@ -107,51 +118,6 @@ std::vector<int32_t> whitespace_tokenize(const std::string &prompt) {
     s = s.substr(sp + 1);
   }
   return t;
-}
-
-// utils.cpp:339-422 sample_top_p_top_k_repeat_penalty
-int32_t sample(const float *logits, int n_logits, std::vector<int32_t> &last_n, double repeat_penalty, int top_k,
-               double top_p, double temp, std::mt19937 &rng) {
-  std::vector<std::pair<double, int32_t>> cand;
-  cand.reserve(n_logits);
-  const double scale = 1.0 / temp;
-  for (int i = 0; i < n_logits; ++i) {
-    if (std::find(last_n.begin(), last_n.end(), i) != last_n.end())
-      cand.push_back({logits[i] < 0.0 ? logits[i] * scale * repeat_penalty : logits[i] * scale / repeat_penalty, i});
-    else
-      cand.push_back({logits[i] * scale, i});
-  }
-  std::partial_sort(cand.begin(), cand.begin() + top_k, cand.end(),
-                    [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) {
-                      return a.first > b.first;
-                    });
-  cand.resize(top_k);
-  double maxl = -INFINITY;
-  for (auto &kv : cand) maxl = std::max(maxl, kv.first);
-  std::vector<double> probs;
-  probs.reserve(cand.size());
-  double sum = 0.0;
-  for (auto &kv : cand) {
-    const double pr = std::exp(kv.first - maxl);
-    probs.push_back(pr);
-    sum += pr;
-  }
-  for (auto &pr : probs) pr /= sum;
-  if (top_p < 1.0f) {
-    double cum = 0.0f;
-    for (int i = 0; i < (int)probs.size(); i++) {
-      cum += probs[i];
-      if (cum >= top_p) {
-        probs.resize(i + 1);
-        cand.resize(i + 1);
-        break;
-      }
-    }
-    cum = 1.0 / cum;
-    for (auto &pr : probs) pr *= cum;
-  }
-  std::discrete_distribution<> dist(probs.begin(), probs.end());
-  return cand[dist(rng)].second;
 }
 
 double now_s() {
@@ -190,7 +156,13 @@ void print_kernel_table(vsim_model *model) {
 
 int run(const Params &params, int arch) {
   const double t_start = now_s();
-  std::mt19937 rng(params.seed);
+  const vsim_sample_params sp = {params.seed,  params.top_k, params.repeat_last_n,
+                                 params.top_p, params.temp,  params.repeat_penalty};
+  vsim_sampler *sampler = nullptr;
+  if (vsim_sampler_create(&sp, &sampler) != VSIM_OK) {
+    fprintf(stderr, "%s: bad sampling parameters: %s\n", __func__, vsim_last_error());
+    return 1;
+  }
   vsim_model *model = nullptr;
   printf("%s: loading model from '%s' - please wait ...\n", __func__, params.model.c_str());
   if (vsim_model_load_file(params.model.c_str(), arch, params.n_ctx, params.device, 0, -1, &model) != VSIM_OK) {
@@ -230,7 +202,6 @@ int run(const Params &params, int arch) {
     fprintf(stderr, "warm-up eval failed: %s\n", vsim_last_error());
     return 1;
   }
-  std::vector<int32_t> last_n(params.repeat_last_n, 0);
   std::vector<int32_t> embd;
   int n_past = 0;
   double t_predict = 0.0, t_sample = 0.0;
@@ -238,9 +209,17 @@ int run(const Params &params, int arch) {
   printf(" embd.size()=%d embd_inp.size()=%d params.n_predict=%d", (int)embd.size(), (int)embd_inp.size(), n_predict);
   printf("\n<|BEGIN> ");
   for (int i = (int)embd.size(); i < (int)embd_inp.size() + n_predict; i++) {
+    // a single-token eval whose logits are only sampled from: the sampled step (top-k on the
+    // device, no logits copy); prompt batches and --return_logits copy the logits row out
+    const bool fused = params.device_sampler && !params.return_logits && embd.size() == 1 &&
+                       i >= (int)embd_inp.size();
+    int32_t fused_id = -1;
     if (!embd.empty()) {
       const double t0 = now_s();
-      if (vsim_model_eval(model, n_past, embd.data(), (int)embd.size(), nullptr, nullptr, logits.data()) != VSIM_OK) {
+      const int rc = fused ? vsim_model_eval_sample(model, sampler, n_past, embd[0], &fused_id)
+                           : vsim_model_eval(model, n_past, embd.data(), (int)embd.size(), nullptr, nullptr,
+                                             logits.data());
+      if (rc != VSIM_OK) {
         printf("Failed to predict\n");
         fprintf(stderr, "%s\n", vsim_last_error());
         return 1;
@@ -255,22 +234,24 @@ int run(const Params &params, int arch) {
       if (params.return_logits) {
         print_logits(logits, true);
         fflush(stdout);
+        vsim_sampler_free(sampler);
         vsim_model_free(model);
         return 0;
       }
       const double t0 = now_s();
-      const int32_t id = sample(logits.data(), hp.n_vocab, last_n, params.repeat_penalty,
-                                (int)(float)params.top_k, params.top_p, params.temp, rng);
-      last_n.erase(last_n.begin());
-      last_n.push_back(id);
+      int32_t id = fused_id;
+      if (!fused && vsim_sampler_sample_host(sampler, logits.data(), hp.n_vocab, &id) != VSIM_OK) {
+        printf("Failed to sample\n");
+        fprintf(stderr, "%s\n", vsim_last_error());
+        return 1;
+      }
       embd.push_back(id);
       t_sample += now_s() - t0;
     } else {
       for (int k = i; k < (int)embd_inp.size(); k++) {
         if (params.return_logits) print_logits(logits, false);
         embd.push_back(embd_inp[k]);
-        last_n.erase(last_n.begin());
-        last_n.push_back(embd_inp[k]);
+        vsim_sampler_accept(sampler, embd_inp[k]);
         if ((int)embd.size() > params.n_batch) break;
       }
       i += (int)embd.size() - 1;
@@ -284,6 +265,13 @@ int run(const Params &params, int arch) {
   printf("\nvsim-hip: load %.3f s, %d evals in %.3f s (%d single-token, %.2f ms/eval), sample %.3f s, total %.3f s\n",
          t_load, n_evals, t_predict, n_decode, n_evals ? 1e3 * t_predict / n_evals : 0.0, t_sample, now_s() - t_start);
   if (profile) print_kernel_table(model);
+  // (with the device sampler the candidate stage's time is inside the evals above, and a token that
+  // follows a prompt batch is still sampled from that eval's logits row on the host)
+  uint64_t picks = 0, host_picks = 0;
+  vsim_sampler_stats(sampler, &picks, &host_picks);
+  printf("vsim-hip: sampler %s: %llu tokens from device top-k, %llu sampled on the host\n",
+         params.device_sampler ? "device" : "host", (unsigned long long)picks, (unsigned long long)host_picks);
+  vsim_sampler_free(sampler);
   vsim_model_free(model);
   return 0;
 }
