@@ -264,6 +264,69 @@ int vsim_gemm_set_tile_order(int cols);
  * straight to the next GEMM's fp16 operand: quantize_row_q4_0 per 32-value block, d*(q-8) as
  * fp16 -- what vsim_op_act_quant_f16 makes of the normalized rows. */
 int vsim_op_norm_f16q(const float *x, int k, int rows, const float *w, const float *b, void *x16, void *stream);
+/* ---- fast-mode decode step, kernel by kernel (fast_decode.hip; the launches of the model's
+ * fast step with the same parameter blocks).  Q4 SoA rows are vsim_op_q4_quantize's xq for n = 1:
+ * the nibble plane [k/32][16], then the k/32 float scales.
+ * Weights are W4T32 (vsim_op_q4_repack) and need VSIM_FAST_PAD readable bytes after the tensor:
+ * the weight stream loads whole batches past a wave's block range (and past the tensor's end)
+ * and zeroes their scales, so allocate vsim_q4_bytes(rows, k) + VSIM_FAST_PAD and repack into the
+ * front.  A bias is read for every row of the last 32-row tile: rows rounded up to 32 floats.
+ * All three enqueue on `stream` and do not synchronize. */
+#define VSIM_FAST_PAD 65536
+enum { VSIM_FE_STORE = 0, VSIM_FE_GELU_Q = 1, VSIM_FE_ROPE_Q = 2, VSIM_FE_ROPE_K = 3, VSIM_FE_V = 4 };
+typedef struct {
+  const void *w;     /* W4T32 rows x k (+ VSIM_FAST_PAD) */
+  int32_t rows, k;   /* rows % 32 == 0 unless epi == VSIM_FE_STORE */
+  const float *bias; /* may be NULL (required for VSIM_FE_GELU_Q) */
+  float *y;          /* STORE, ROPE_Q: [rows]; ROPE_K, V: a cache [n_ctx][rows], row *n_past is written */
+  int32_t epi;       /* VSIM_FE_* */
+  int32_t act;       /* activation 0 or 1 */
+} vsim_fast_job;
+typedef struct {
+  /* the two activations, either Q4 SoA rows of k values (lnx == NULL) ... */
+  const void *xq[2];
+  /* ... or the LayerNorm (ggml.c:4246-4304, both moments in one double pass) of the row lnx [k]
+   * with affine act, quantized (ggml.c:209-251) in every workgroup's prologue */
+  const float *lnx, *lnw[2], *lnb[2];
+  vsim_fast_job j[4]; /* every k equal, a multiple of 32, at most 8192 */
+  int32_t nj;
+  void *oq;           /* VSIM_FE_GELU_Q: gelu table (vsim_op_tables) of fp16(dot + bias), quantized:
+                         Q4 SoA row of that job's `rows` values */
+  /* VSIM_FE_ROPE_Q / _K: rotation at position *n_past (device), cs [pos][n_rot/2] {cos, sin}
+   * doubles; style 0 rotate-half (d % 32 == 0, n_rot <= 32), 1 GPT-J pairs; head dim d.
+   * VSIM_FE_V reads *n_past too. */
+  const int32_t *n_past;
+  const double *cs;
+  int32_t d, n_rot, style;
+  uint32_t *clear;    /* may be NULL: nclear words zeroed by the launch */
+  int32_t nclear;
+} vsim_fast_gemv_args;
+/* One k_fast_gemv batch: the 32-row tiles of up to 4 jobs, y = W . q4(x) (+ bias), the integer
+ * block dots scaled by d_w d_x and summed in a fixed order. */
+int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream);
+typedef struct {
+  /* fc_out split over K: ffp[s][rows] = rows of wf over blocks [s nb/sf, (s+1) nb/sf) of xf */
+  const void *wf;    /* W4T32 rows x k (+ VSIM_FAST_PAD); rows % 32 == 0, (k/32) % sf == 0, k/sf <= 8192 */
+  int32_t rows, k, sf;
+  const void *xf;    /* Q4 SoA row of k values */
+  float *ffp;        /* [sf][rows] */
+  /* single-query attention at position *n_past over 64-position chunks: q [H d] (rotated), kc, vc
+   * [>= *n_past + 1][H d] with the new row in place; part [H][nchunk][d + 2] receives every
+   * chunk's (max, sum, weighted V) (chunks past *n_past: -inf, 0), oq the merged output as a
+   * Q4 SoA row of H d values.  d % 32 == 0, d <= 256, nchunk <= 64, *n_past < 64 nchunk. */
+  const float *q, *kc, *vc;
+  const int32_t *n_past;
+  int32_t d, H, nchunk;
+  float scale;
+  float *part;
+  uint32_t *hcnt;    /* 4 H words of workspace: zeroed on the stream by this call */
+  void *oq;
+} vsim_fast_tail_args;
+int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream);
+/* k_fast_oproj_join: out = x + ((W . xq + bo) + (sum_s ffp[s] + bproj)), W E x E W4T32 (+ VSIM_FAST_PAD),
+ * xq the attention's Q4 SoA row, ffp [sf][E]; bo may be NULL.  E % 32 == 0, E <= 8192. */
+int vsim_op_fast_oproj_join(const void *w, int E, const void *xq, const float *bo, const float *ffp, int sf,
+                            const float *bproj, const float *x, float *out, void *stream);
 /* device fp16 tables (exp, gelu) as built by ggml_init (ggml.c:1240-1251) */
 int vsim_op_tables(uint16_t *exp_f16_host, uint16_t *gelu_f16_host);
 
@@ -322,6 +385,9 @@ int vsim_model_get_tensor(vsim_model *m, const char *name, void *host, size_t nb
 /* Synthetic weights drawn on the device (N(0,std), LN gains 1+N(0,std)), quantized with
  * quantize_row_q4_0 semantics; for throughput runs of full-size configs. */
 int vsim_model_randomize(vsim_model *m, uint64_t seed, float std);
+/* VSIM_MODE_FAST on a model whose n_ctx exceeds 4096 (more than 64 chunks of 64 positions, the
+ * limit of the fast decode step's attention merge) selects VSIM_MODE_EXACT: every eval of such a
+ * model is the exact one, bit for bit. */
 int vsim_model_set_mode(vsim_model *m, int mode);
 /* Allocates ahead what a prompt of up to n_tokens sets up on its first eval (the N-token
  * scratch, the fp16 key copies of the prompt attention, the GEMMs' stream-K workspace) and

@@ -9,6 +9,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from fast_ref import q4_f16_ref as _q4_f16_ref  # noqa: E402
 from golden_util import cases, ops  # noqa: E402
 from vsim_amd import hip  # noqa: E402
 from vsim_amd import modelgen as mg  # noqa: E402
@@ -755,19 +756,6 @@ def test_prefill_gemm_qk_pair(M, K, N, p0):
     assert bool((err <= tol + 1e-30).all()), float((err / (tol + 1e-30)).max())
     if M * 2 // 256 * ((N + 255) // 256) > 256:
         assert int((err > 0).sum()) > 0  # (the split really ran)
-
-
-def _q4_f16_ref(y):
-    """quantize_row_q4_0 (ggml.c:209-251) per 32-block of the f32 rows y, the values d*(q-8)
-    rounded once to fp16 (the prompt GEMMs' operand)."""
-    b = y.reshape(-1, 32).astype(np.float32)
-    amax = np.abs(b).max(axis=1).astype(np.float32)
-    d = (amax / np.float32(7.0)).astype(np.float32)
-    with np.errstate(divide="ignore"):
-        idv = np.where(d != 0, np.float32(1.0) / d, np.float32(0.0)).astype(np.float32)
-    t = (b * idv[:, None]).astype(np.float32)
-    q = np.where(t >= 0, np.floor(t + 0.5), -np.floor(-t + 0.5))  # round half away from zero
-    return (d[:, None].astype(np.float64) * q).astype(np.float16).reshape(y.shape)
 
 
 @pytest.mark.parametrize("k,rows", [(6144, 300), (4096, 257), (1024, 64), (5120, 33), (2080, 20)])

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "fast.hpp"
 #include "graph.hpp"
 #include "../../include/vsim_hip.h"
 
@@ -201,6 +202,115 @@ int vsim_op_attn_prefill_q16(const float *Q, const float *kc, const float *vc, i
                              float scale, void *out16, void *stream) {
   return launch_attn_prefill_f16(Q, kc, vc, d, H, N, n_past, scale, nullptr, (hipStream_t)stream, nullptr, 0, false,
                                  out16);
+}
+// ---- the fast decode step's launches (fast_decode.hip) on caller buffers.  The launchers
+// check the shapes the kernels stage in LDS; the checks here are the ones the model's own
+// shapes make unnecessary (null operands, whole tiles where a kernel writes all 32 rows).
+static_assert(FD_PAD == VSIM_FAST_PAD, "include/vsim_hip.h states the weight slack");
+static inline const uint8_t *soa_qs(const void *xq) { return (const uint8_t *)xq; }
+static inline float *soa_d(const void *xq, int k) { return (float *)((uint8_t *)xq + (size_t)(k / QK) * 16); }
+
+int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
+  if (!a || a->nj < 1 || a->nj > 4) { set_error("fast_gemv: 1 to 4 jobs"); return VSIM_EINVAL; }
+  const int K = a->j[0].k;
+  if (K <= 0 || K % QK) { set_error("fast_gemv: k must be a positive multiple of 32"); return VSIM_EINVAL; }
+  FastGemv P{};
+  P.nj = a->nj;
+  bool rope = false, pos = false;
+  for (int i = 0; i < a->nj; ++i) {
+    const vsim_fast_job &j = a->j[i];
+    const bool whole = j.rows % T32 == 0;
+    if (!j.w || j.rows <= 0 || j.k != K || j.epi < FE_STORE || j.epi > FE_V || (j.act != 0 && j.act != 1) ||
+        (j.epi != FE_GELU_Q && !j.y) || (j.epi != FE_STORE && !whole) || (j.epi == FE_GELU_Q && (!j.bias || !a->oq)) ||
+        (a->lnx ? !a->lnw[j.act] || !a->lnb[j.act] : !a->xq[j.act])) {
+      set_error("fast_gemv: bad job (operand missing, k differs, or a partial tile under a non-store epilogue)");
+      return VSIM_EINVAL;
+    }
+    rope |= j.epi == FE_ROPE_Q || j.epi == FE_ROPE_K;
+    pos |= j.epi >= FE_ROPE_Q;
+    if (j.epi == FE_GELU_Q) {
+      P.oq_qs = (uint8_t *)a->oq;
+      P.oq_d = soa_d(a->oq, j.rows);
+    }
+    P.j[i] = FastJob{w4_view(j.w, j.rows, j.k), j.bias, j.y, j.epi, j.act};
+  }
+  if (pos && !a->n_past) { set_error("fast_gemv: n_past missing"); return VSIM_EINVAL; }
+  if (rope && (!a->cs || a->d <= 0 || a->n_rot <= 0 || a->n_rot % 2 || a->n_rot > a->d || (a->style != 0 && a->style != 1) ||
+               (a->style == 0 ? a->d % T32 != 0 || a->n_rot > T32 : a->d % 2 != 0))) {
+    set_error("fast_gemv: RoPE needs cs, an even n_rot <= d, and its pairs inside one 32-row tile");
+    return VSIM_EINVAL;
+  }
+  if (a->clear && a->nclear < 0) { set_error("fast_gemv: nclear < 0"); return VSIM_EINVAL; }
+  for (int i = 0; i < 2; ++i) {
+    P.xq[i] = a->lnx ? nullptr : soa_qs(a->xq[i]);
+    P.xd[i] = a->lnx || !a->xq[i] ? nullptr : soa_d(a->xq[i], K);
+    P.lnw[i] = a->lnw[i];
+    P.lnb[i] = a->lnb[i];
+  }
+  P.lnx = a->lnx;
+  DevTables tab;
+  RC(tables_get(&tab));
+  P.gelu_tab = tab.gelu_f16;
+  P.npast = a->n_past;
+  P.cs = (const double2 *)a->cs;
+  P.d = rope ? a->d : 1;
+  P.n_rot = a->n_rot;
+  P.style = a->style;
+  P.clear = a->clear;
+  P.nclear = a->clear ? a->nclear : 0;
+  return launch_fast_gemv(P, K, (hipStream_t)stream);
+}
+
+int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream) {
+  if (!a || !a->wf || !a->xf || !a->ffp || !a->q || !a->kc || !a->vc || !a->n_past || !a->part || !a->hcnt || !a->oq) {
+    set_error("fast_tail: null argument");
+    return VSIM_EINVAL;
+  }
+  if (a->rows <= 0 || a->rows % T32 || a->k <= 0 || a->k % QK || a->sf < 1 || a->sf > 8 || a->d <= 0 || a->H < 1 ||
+      a->nchunk < 1) {
+    set_error("fast_tail: bad shape (whole 32-row tiles, k a multiple of 32, 1 <= sf <= 8)");
+    return VSIM_EINVAL;
+  }
+  FastTail T{};
+  T.wf = w4_view(a->wf, a->rows, a->k);
+  T.xf_qs = soa_qs(a->xf);
+  T.xf_d = soa_d(a->xf, a->k);
+  T.ffp = a->ffp;
+  T.sf = a->sf;
+  T.q = a->q;
+  T.kc = a->kc;
+  T.vc = a->vc;
+  T.npast = a->n_past;
+  T.d = a->d;
+  T.H = a->H;
+  T.nchunk = a->nchunk;
+  T.scale = a->scale;
+  T.part = a->part;
+  T.hcnt = a->hcnt;
+  T.oq_qs = (uint8_t *)a->oq;
+  T.oq_d = soa_d(a->oq, a->d * a->H);
+  // the per-head counters are this call's (the model zeroes them from the layer's GEMV launch)
+  VSIM_HIP(hipMemsetAsync(a->hcnt, 0, (size_t)4 * a->H * sizeof(unsigned), (hipStream_t)stream));
+  return launch_fast_tail(T, (hipStream_t)stream);
+}
+
+int vsim_op_fast_oproj_join(const void *w, int E, const void *xq, const float *bo, const float *ffp, int sf,
+                            const float *bproj, const float *x, float *out, void *stream) {
+  if (!w || !xq || !ffp || !bproj || !x || !out || E <= 0 || E % QK || sf < 1 || sf > 8) {
+    set_error("fast_oproj_join: bad argument");
+    return VSIM_EINVAL;
+  }
+  FastOproj O{};
+  O.w = w4_view(w, E, E);
+  O.xq = soa_qs(xq);
+  O.xd = soa_d(xq, E);
+  O.bo = bo;
+  O.ffp = ffp;
+  O.sf = sf;
+  O.bproj = bproj;
+  O.x = x;
+  O.out = out;
+  return launch_fast_oproj_join(O, (hipStream_t)stream);
 }
 int vsim_op_tables(uint16_t *exp_f16_host, uint16_t *gelu_f16_host) { return tables_host(exp_f16_host, gelu_f16_host); }
 int vsim_gemm_set_streamk(int enable) { return gemm_set_streamk(enable); }

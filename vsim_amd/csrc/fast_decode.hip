@@ -546,7 +546,6 @@ __device__ __forceinline__ void fast_fcout_part(const FastTail &A, int idx, uint
 // out-projection's Q4 input.  Run by wave 0 of the chunk workgroup that counts last for the
 // head, behind one agent acquire (the partials were stored sc1).  Four consecutive outputs
 // per lane, a 32-block = 8 lanes; chunks past n_past weigh zero.
-constexpr int FD_MAXCH = 64;  // chunks per head (n_ctx <= 4096)
 __device__ void fast_merge_head(const FastTail &A, int h, int lane) {
   const int d = A.d, nch = A.nchunk;
   const int nv = min(*A.npast / FD_CHUNK + 1, nch);  // chunks holding positions 0 .. n_past

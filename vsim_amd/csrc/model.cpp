@@ -767,7 +767,8 @@ bool fast_decode_ok(const vsim_model *m) {
   const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
   return d % 32 == 0 && d <= 256 && E <= 8192 && E % 128 == 0 &&
          (m->arch == VSIM_ARCH_GPTJ || (m->arch == VSIM_ARCH_GPTNEOX && m->hp.use_parallel_residual == 1)) &&
-         (m->arch == VSIM_ARCH_GPTJ || m->hp.n_rot <= 32) && 2 * H * nch <= 4096;
+         (m->arch == VSIM_ARCH_GPTJ || m->hp.n_rot <= 32) && 2 * H * nch <= 4096 &&
+         nch <= FD_MAXCH;  // (launch_fast_tail's limit: a longer context takes the exact step)
 }
 
 int enqueue_decode_fast(vsim_model *m, int &nk) {
@@ -1521,7 +1522,10 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
 
 int vsim_model_set_mode(vsim_model *m, int mode) {
   if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST) { set_error("set_mode: bad mode"); return VSIM_EINVAL; }
-  m->mode = mode;
+  // A context of more than FD_MAXCH chunks is beyond the fast decode step's merge
+  // (launch_fast_tail refuses it): such a model runs in exact mode throughout
+  const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
+  m->mode = mode == VSIM_MODE_FAST && nch > FD_MAXCH ? VSIM_MODE_EXACT : mode;
   return VSIM_OK;
 }
 

@@ -33,7 +33,7 @@ EXPORTS = [
     "vsim_op_gemm_q4_256", "vsim_op_get_rows",
     "vsim_op_norm", "vsim_op_gelu", "vsim_op_argmax", "vsim_op_attn_softmax", "vsim_op_rope", "vsim_op_kq", "vsim_op_kqv", "vsim_op_kq_causal", "vsim_op_kqv_causal",
     "vsim_op_attn_prefill", "vsim_op_attn_prefill_q16", "vsim_gemm_set_streamk", "vsim_gemm_set_qk_pair", "vsim_gemm_set_tile_order", "vsim_op_gemm_q4_256_pair", "vsim_op_norm_f16q",
-    "vsim_op_tables",
+    "vsim_op_tables", "vsim_op_fast_gemv", "vsim_op_fast_tail", "vsim_op_fast_oproj_join",
     "vsim_model_create", "vsim_model_load_file", "vsim_model_set_tensor", "vsim_model_get_tensor",
     "vsim_model_randomize",
     "vsim_model_set_mode", "vsim_model_reserve", "vsim_model_hparams", "vsim_model_eval", "vsim_model_eval_argmax", "vsim_model_generate",
@@ -100,6 +100,32 @@ class SampleParams(ctypes.Structure):
                 ("top_p", ctypes.c_float), ("temp", ctypes.c_float), ("repeat_penalty", ctypes.c_float)]
 
 
+# the fast decode step's launches (vsim_op_fast_* in include/vsim_hip.h)
+FAST_PAD = 65536  # VSIM_FAST_PAD: readable bytes a weight needs after its last block
+FE_STORE, FE_GELU_Q, FE_ROPE_Q, FE_ROPE_K, FE_V = range(5)
+
+
+class FastJob(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p), ("rows", ctypes.c_int32), ("k", ctypes.c_int32), ("bias", ctypes.c_void_p),
+                ("y", ctypes.c_void_p), ("epi", ctypes.c_int32), ("act", ctypes.c_int32)]
+
+
+class FastGemvArgs(ctypes.Structure):
+    _fields_ = [("xq", ctypes.c_void_p * 2), ("lnx", ctypes.c_void_p), ("lnw", ctypes.c_void_p * 2),
+                ("lnb", ctypes.c_void_p * 2), ("j", FastJob * 4), ("nj", ctypes.c_int32), ("oq", ctypes.c_void_p),
+                ("n_past", ctypes.c_void_p), ("cs", ctypes.c_void_p), ("d", ctypes.c_int32),
+                ("n_rot", ctypes.c_int32), ("style", ctypes.c_int32), ("clear", ctypes.c_void_p),
+                ("nclear", ctypes.c_int32)]
+
+
+class FastTailArgs(ctypes.Structure):
+    _fields_ = [("wf", ctypes.c_void_p), ("rows", ctypes.c_int32), ("k", ctypes.c_int32), ("sf", ctypes.c_int32),
+                ("xf", ctypes.c_void_p), ("ffp", ctypes.c_void_p), ("q", ctypes.c_void_p), ("kc", ctypes.c_void_p),
+                ("vc", ctypes.c_void_p), ("n_past", ctypes.c_void_p), ("d", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("nchunk", ctypes.c_int32), ("scale", ctypes.c_float), ("part", ctypes.c_void_p),
+                ("hcnt", ctypes.c_void_p), ("oq", ctypes.c_void_p)]
+
+
 class HParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("n_vocab", "n_embd", "n_head", "n_layer", "n_rot", "use_parallel_residual")]
@@ -148,6 +174,9 @@ def lib():
     L.vsim_op_gemm_q4_256_pair.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp]
     L.vsim_op_norm_f16q.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.vsim_op_tables.argtypes = [vp, vp]
+    L.vsim_op_fast_gemv.argtypes = [ctypes.POINTER(FastGemvArgs), vp]
+    L.vsim_op_fast_tail.argtypes = [ctypes.POINTER(FastTailArgs), vp]
+    L.vsim_op_fast_oproj_join.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
     L.vsim_model_create.argtypes = [ci, ctypes.POINTER(HParams), ci, ci, ci, ci, ctypes.POINTER(vp)]
     L.vsim_model_load_file.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
     L.vsim_model_set_tensor.argtypes = [vp, ctypes.c_char_p, vp, sz]
@@ -277,6 +306,32 @@ def topk(x, n, win, scale, repeat_penalty, k, val, ids, stream=None):
     nw = 0 if win is None else int(win.numel() if hasattr(win, "numel") else win.size)
     check(lib().vsim_op_topk(addr(x), n, addr(win) if nw else None, nw, float(scale), float(repeat_penalty), k,
                              addr(val), addr(ids), stream), "topk")
+
+
+def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,
+              d=0, n_rot=0, style=0, clear=None, nclear=0, stream=None):
+    """vsim_op_fast_gemv: jobs = [(w, rows, k, bias, y, epi, act)], operands torch tensors or None."""
+    a = FastGemvArgs()
+    for i in range(2):
+        a.xq[i], a.lnw[i], a.lnb[i] = ptr(xq[i]), ptr(lnw[i]), ptr(lnb[i])
+    a.lnx, a.oq, a.n_past, a.cs, a.clear = ptr(lnx), ptr(oq), ptr(n_past), ptr(cs), ptr(clear)
+    a.d, a.n_rot, a.style, a.nclear, a.nj = d, n_rot, style, nclear, len(jobs)
+    for i, (w, rows, k, bias, y, epi, act) in enumerate(jobs[:4]):
+        a.j[i] = FastJob(ptr(w), rows, k, ptr(bias), ptr(y), epi, act)
+    check(lib().vsim_op_fast_gemv(ctypes.byref(a), stream), "fast_gemv")
+
+
+def fast_tail(wf, rows, k, sf, xf, ffp, q, kc, vc, n_past, d, H, nchunk, scale, part, hcnt, oq, stream=None):
+    """vsim_op_fast_tail on torch tensors."""
+    a = FastTailArgs(ptr(wf), rows, k, sf, ptr(xf), ptr(ffp), ptr(q), ptr(kc), ptr(vc), ptr(n_past), d, H, nchunk,
+                     float(scale), ptr(part), ptr(hcnt), ptr(oq))
+    check(lib().vsim_op_fast_tail(ctypes.byref(a), stream), "fast_tail")
+
+
+def fast_oproj_join(w, E, xq, bo, ffp, sf, bproj, x, out, stream=None):
+    """vsim_op_fast_oproj_join on torch tensors (bo may be None)."""
+    check(lib().vsim_op_fast_oproj_join(ptr(w), E, ptr(xq), ptr(bo), ptr(ffp), sf, ptr(bproj), ptr(x), ptr(out),
+                                        stream), "fast_oproj_join")
 
 
 class Model:
