@@ -17,7 +17,10 @@
  *     per token is the token ids in and one logits row out (vsim.cpp:736-737), or, for the
  *     greedy and the sampled step, a token id or at most 64 (value, id) candidates out.
  *  plus the sampler object (vsim_sampler_*): the reference's sampler with its O(n_vocab)
- *     stage on the device.
+ *     stage on the device,
+ *  and the model quantizer (vsim_op_q4_quantize_w, vsim_model_load_file_ex,
+ *     vsim_model_set_tensor_src, vsim_quantize_file): the converters' F32 / F16 files to Q4_0
+ *     with the semantics of the reference's quantize_* tools, while loading or file to file.
  *
  * Device weight layout ("W4T32"): a Q4_0 matrix of M rows x K weights keeps the
  * reference's 0.625 B/weight but splits the 20-byte blocks (ggml.c:204-251) into a
@@ -139,6 +142,28 @@ int vsim_op_act_unpack(const void *xq, void *aos, int n, int k, void *stream);
 /* quantize_row_q4_0 (ggml.c:209-251) of n rows of k floats: xq in Q4 SoA, xd = the
  * dequantized values d*(q-8) the exact GEMV multiplies with (ggml.c:497-498). */
 int vsim_op_q4_quantize(const float *x, int k, int n, void *xq, float *xd, void *stream);
+/* The model quantizer's kernel (k_quantize_w): ggml_quantize_q4_0 (utils.cpp:425-482, as
+ * quantize_gptneox.cpp:143-311 drives it) of `rows` rows of k F32 or F16 weights, x a row-major
+ * device buffer (16-byte aligned, k % 32 == 0; F16 is widened exactly, subnormals kept).
+ *   w     W4T32 target: an existing weight of w_rows rows x k, of which rows [row0, row0 + rows)
+ *         are written (row0 % 32 == 0), so a tensor can be quantized in row chunks.  The chunk
+ *         that ends the tensor (row0 + rows == w_rows) also writes the last tile's padding rows
+ *         as vsim_op_q4_repack does (d = 0, nibbles 0x88).  May be NULL.
+ *   aos   the file format: rows * k/32 row-major 20-byte blocks of this chunk.  May be NULL.
+ *   hist  16 device words the caller zeroes: hist[code] += 1 for every weight of the chunk
+ *         (padding rows are never counted; integer adds, so the order does not matter).  May be NULL.
+ * w and aos may both be given; one of them must be.  VSIM_EINVAL for k % 32 != 0, row0 % 32 != 0,
+ * row0 + rows > w_rows, both targets NULL, a bad src_type or a misaligned pointer.  Enqueued on
+ * stream, not synchronized.
+ * The one difference from vsim_op_q4_quantize (quantize_row_q4_0): the weight quantizer takes
+ * amax with std::max(amax, fabsf(v)), under which a NaN weight is IGNORED -- the block keeps the
+ * d of its other values and the NaN element gets code 8 -- where the activation quantizer's MAX
+ * macro lets a NaN replace the running maximum.  A +-Inf weight gives d = inf and every code 8; a
+ * block whose d is so small that 1/d overflows gives every code 8 (the x86 cast of inf and NaN). */
+#define VSIM_SRC_F32 0
+#define VSIM_SRC_F16 1
+int vsim_op_q4_quantize_w(const void *x, int src_type, int rows, int k, void *w, int w_rows, int row0, void *aos,
+                          uint64_t *hist, void *stream);
 /* y[n][M] = W[M][K] . q4_0(x)[n][K] (+ bias[M] if bias != NULL, added after the dot
  * as ggml_add does, vsim.cpp:545-547) */
 int vsim_op_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias,
@@ -380,6 +405,26 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
                          vsim_model **out);
 /* Upload one tensor by its ggml-file name (Q4_0 tensors in the on-disk AoS format). */
 int vsim_model_set_tensor(vsim_model *m, const char *name, const void *host, size_t nbytes);
+/* Load with options.  flags = 0 is vsim_model_load_file exactly.  VSIM_LOAD_QUANTIZE also accepts
+ * the converters' F32 / F16 files (header f16 = 0 / 1): a 2-D record whose slot is a Q4_0 matrix
+ * may then have ftype 0 or 1 and is quantized on the device as it streams in
+ * (vsim_model_set_tensor_src's path, read straight into the staging buffers), or ftype 2 as
+ * before; the same shape, name, missing-tensor and truncation checks apply. */
+#define VSIM_LOAD_QUANTIZE 1
+int vsim_model_load_file_ex(const char *path, int arch, int n_ctx, int device, int layer_begin, int layer_end,
+                            int flags, vsim_model **out);
+/* Upload one matrix as the converters write it (src_type VSIM_SRC_F32 / VSIM_SRC_F16, row-major
+ * [rows][k]) and quantize it into the slot with the reference quantizer's semantics
+ * (vsim_op_q4_quantize_w).  The matrix goes through two pinned staging buffers in chunks of rows
+ * (multiples of 32; about 64 MiB of source by default), the copy of one chunk overlapping the
+ * kernel of the one before, so staging memory is bounded whatever the tensor's size.  BLOOM's
+ * fused query_key_value is spread over its three slots as vsim_model_set_tensor does.  A 1-D
+ * (F32) tensor takes vsim_model_set_tensor's path (src_type must be VSIM_SRC_F32). */
+int vsim_model_set_tensor_src(vsim_model *m, const char *name, const void *host, size_t nbytes, int src_type);
+/* Rows per staging chunk of the two calls above, process-wide: 0 = the default, other values are
+ * rounded up to a multiple of 32.  Returns the previous value.  For tests: many chunks on tiny
+ * tensors. */
+int vsim_quantize_set_chunk_rows(int rows);
 /* Read one tensor back in the same file format (Q4_0 as AoS blocks, F32 as floats). */
 int vsim_model_get_tensor(vsim_model *m, const char *name, void *host, size_t nbytes);
 /* Synthetic weights drawn on the device (N(0,std), LN gains 1+N(0,std)), quantized with
@@ -463,6 +508,28 @@ int vsim_model_profile_kernel(vsim_model *m, int i, char *name, int name_cap, do
                               double *bytes);
 int vsim_model_profile_stats(vsim_model *m, double *gemv_ms, long *gemv_launches, double *gemv_bytes);
 void vsim_model_free(vsim_model *m);
+
+/* ------------------------------------------------------------- 4. file quantizer ---- */
+/* The reference's quantize_gptneox / quantize_gptj / quantize_bloom (type 2, Q4_0) as one call:
+ * magic, header and vocab are copied with the header's last field (f16) set to 2; a record that is
+ * 2-D and whose name ends in "weight" must have ftype 0 (F32) or 1 (F16) and is rewritten as Q4_0
+ * (ftype 2, vsim_op_q4_quantize_w's semantics, NaN rule included); every other record is copied
+ * byte for byte.  The file streams through in row chunks, so memory is bounded and record sizes
+ * are size_t.  device >= 0: k_quantize_w's AoS output on that GPU; device == -1: a plain host
+ * loop with the same semantics (no GPU needed).  Failures are VSIM_EFILE with a reason (bad magic;
+ * a truncated header, vocab or record; a 2-D weight of ftype 2 or 3; ne[0] % 32 != 0; an unknown
+ * ftype) and remove the partly written output file.
+ * st (may be NULL): the histogram of all codes, the bytes read and written, the records
+ * quantized and copied. */
+typedef struct {
+  uint64_t hist[16];
+  uint64_t bytes_in, bytes_out;
+  int32_t n_quantized, n_copied;
+} vsim_quantize_stats;
+int vsim_quantize_file(const char *in, const char *out, int arch, int device, vsim_quantize_stats *st);
+/* 1: vsim_quantize_file prints one line per record to stdout (name, shape, source type, sizes,
+ * the record's histogram as fractions) and the totals.  Process-wide; returns the previous value. */
+int vsim_quantize_set_verbose(int on);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,10 @@ int vsim_op_act_unpack(const void *xq, void *aos, int n, int k, void *stream) {
 int vsim_op_q4_quantize(const float *x, int k, int n, void *xq, float *xd, void *stream) {
   return launch_q4_quantize(x, k, n, xq, xd, (hipStream_t)stream);
 }
+int vsim_op_q4_quantize_w(const void *x, int src_type, int rows, int k, void *w, int w_rows, int row0, void *aos,
+                          uint64_t *hist, void *stream) {
+  return launch_quantize_w(x, src_type, rows, k, w, w_rows, row0, aos, hist, (hipStream_t)stream);
+}
 int vsim_op_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias, float *y,
                     int mode, void *stream) {
   return launch_q4_gemv(w, M, K, xq, xd, n, bias, y, mode, (hipStream_t)stream);

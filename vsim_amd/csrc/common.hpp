@@ -291,6 +291,9 @@ int spin_timeouts(unsigned *out);            // waits that gave up, summed over 
 int launch_q4_repack(const void *aos, void *soa, int rows, int k, hipStream_t s);
 int launch_q4_unpack(const void *soa, void *aos, int rows, int k, hipStream_t s);
 int launch_q4_quantize(const float *x, int k, int n, void *xq, float *xd, hipStream_t s);
+// the model quantizer (quantize_w.hip): vsim_op_q4_quantize_w
+int launch_quantize_w(const void *x, int src_type, int rows, int k, void *w, int w_rows, int row0, void *aos,
+                      uint64_t *hist, hipStream_t s);
 int launch_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias,
                    float *y, int mode, hipStream_t s);
 int launch_gemv_batch(const GemvBatch &B, int mode, hipStream_t s);

@@ -14,6 +14,8 @@
 // the captured and the eager form are the same call).  LAUNCH brackets a profiled launch.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -146,6 +148,16 @@ struct vsim_model {
   bool borrowed = false;
   int kqv_nth = 1;
   float attn_scale = 0.0f;
+
+  // F32 / F16 sources on their way to Q4_0 (vsim_model_set_tensor_src, the quantizing loader): two
+  // pinned host buffers and their device twins of `cap` bytes each, the copy stream, and per buffer
+  // the events "copied to the device" and "quantized"; allocated on first use (quant_reserve)
+  struct QuantStage {
+    void *host[2] = {nullptr, nullptr}, *dev[2] = {nullptr, nullptr};
+    size_t cap = 0;
+    hipStream_t copy = nullptr;
+    hipEvent_t copied[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+  } qstage;
 
   // Per-kernel profiling (bench.py's live roofline): with profiling on, the decode step runs
   // eagerly and an event pair brackets every launch, tagged with the kernel's name and the
@@ -1297,6 +1309,101 @@ int model_create_impl(int arch, const vsim_hparams *hp, int n_ctx, int device, i
 
 // The borrowed model's per-call settings: the reference pool's KQV grouping (cgraph->n_threads)
 // and the graph's own attention scale; a change drops the captured decode graphs.
+}  // namespace vsim
+
+// ---------------------------------------------------------------- F32 / F16 sources -> Q4_0
+namespace {
+
+std::atomic<int> g_quant_chunk_rows{0};             // vsim_quantize_set_chunk_rows (0: default)
+constexpr size_t QUANT_CHUNK_BYTES = (size_t)64 << 20;  // default source bytes per staging chunk
+
+int quant_chunk_rows(int k, size_t esz) {
+  long long c = g_quant_chunk_rows.load();
+  if (c <= 0) c = (long long)(QUANT_CHUNK_BYTES / ((size_t)k * esz));
+  c = (c + T32 - 1) / T32 * T32;
+  return (int)std::max<long long>(T32, std::min<long long>(c, 1 << 30));
+}
+
+void quant_release(vsim_model *m) {
+  vsim_model::QuantStage &q = m->qstage;
+  for (int b = 0; b < 2; ++b) {
+    if (q.host[b]) (void)hipHostFree(q.host[b]);
+    if (q.dev[b]) (void)hipFree(q.dev[b]);
+    if (q.copied[b]) (void)hipEventDestroy(q.copied[b]);
+    if (q.done[b]) (void)hipEventDestroy(q.done[b]);
+  }
+  if (q.copy) (void)hipStreamDestroy(q.copy);
+  q = vsim_model::QuantStage();
+}
+
+int quant_reserve(vsim_model *m, size_t bytes) {
+  vsim_model::QuantStage &q = m->qstage;
+  if (!q.copy) {
+    VSIM_HIP(hipStreamCreateWithFlags(&q.copy, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+      VSIM_HIP(hipEventCreateWithFlags(&q.copied[b], hipEventDisableTiming));
+      VSIM_HIP(hipEventCreateWithFlags(&q.done[b], hipEventDisableTiming));
+    }
+  }
+  if (bytes <= q.cap) return VSIM_OK;
+  for (int b = 0; b < 2; ++b) {
+    if (q.host[b]) (void)hipHostFree(q.host[b]);
+    if (q.dev[b]) (void)hipFree(q.dev[b]);
+    q.host[b] = q.dev[b] = nullptr;
+  }
+  q.cap = 0;
+  for (int b = 0; b < 2; ++b) {
+    VSIM_HIP(hipHostMalloc(&q.host[b], bytes, hipHostMallocDefault));
+    VSIM_HIP(hipMalloc(&q.dev[b], bytes));
+  }
+  q.cap = bytes;
+  return VSIM_OK;
+}
+
+// Quantize a [s.rows][s.k] matrix of src_type into the Q4_0 slot s.  `next(dst, n)` delivers the
+// next n source bytes (rows in order) into pinned memory and returns false when the source ends
+// early (-> QUANT_SHORT).  Chunk i goes host[i & 1] -> dev[i & 1] on the copy stream, then
+// k_quantize_w on the model's stream: the copy of chunk i + 1 overlaps the kernel of chunk i, and
+// a buffer pair is reused only after its copy (host side) and its kernel (device side) finished.
+constexpr int QUANT_SHORT = 1;
+template <typename Next>
+int quantize_into_slot(vsim_model *m, Slot &s, int src_type, Next next) {
+  const size_t esz = src_type == VSIM_SRC_F16 ? 2 : 4, row_bytes = (size_t)s.k * esz;
+  const int chunk = std::min(quant_chunk_rows(s.k, esz), (s.rows + T32 - 1) / T32 * T32);
+  RC(quant_reserve(m, (size_t)chunk * row_bytes));
+  vsim_model::QuantStage &q = m->qstage;
+  int rc = VSIM_OK, i = 0;
+  auto hip = [&](hipError_t e, const char *what) {
+    if (e != hipSuccess && rc == VSIM_OK) rc = hip_fail(e, what);
+    return e == hipSuccess;
+  };
+  for (int r0 = 0; r0 < s.rows && rc == VSIM_OK; r0 += chunk, ++i) {
+    const int b = i & 1, n = std::min(chunk, s.rows - r0);
+    if (i >= 2) {
+      if (!hip(hipEventSynchronize(q.copied[b]), "quantize: wait for the staging copy")) break;
+      if (!hip(hipStreamWaitEvent(q.copy, q.done[b], 0), "quantize: order the staging copy")) break;
+    }
+    if (!next(q.host[b], (size_t)n * row_bytes)) { rc = QUANT_SHORT; break; }
+    if (!hip(hipMemcpyAsync(q.dev[b], q.host[b], (size_t)n * row_bytes, hipMemcpyHostToDevice, q.copy),
+             "quantize: upload"))
+      break;
+    if (!hip(hipEventRecord(q.copied[b], q.copy), "quantize: record")) break;
+    if (!hip(hipStreamWaitEvent(m->stream, q.copied[b], 0), "quantize: order the kernel")) break;
+    rc = launch_quantize_w(q.dev[b], src_type, n, s.k, s.ptr, s.rows, r0, nullptr, nullptr, m->stream);
+    if (rc != VSIM_OK) break;
+    if (!hip(hipEventRecord(q.done[b], m->stream), "quantize: record")) break;
+  }
+  // nothing of this call stays in flight, whatever happened
+  const hipError_t e1 = hipStreamSynchronize(q.copy), e2 = hipStreamSynchronize(m->stream);
+  hip(e1, "quantize: copy stream");
+  hip(e2, "quantize: kernel stream");
+  if (rc == VSIM_OK) s.loaded = true;
+  return rc;
+}
+
+}  // namespace
+
+namespace vsim {
 int model_set_attn(vsim_model *m, int kqv_nth, float scale) {
   if (kqv_nth < 1) kqv_nth = 1;
   if (m->kqv_nth == kqv_nth && m->attn_scale == scale) return VSIM_OK;
@@ -1320,6 +1427,7 @@ void vsim_model_free(vsim_model *m) {
   (void)hipSetDevice(m->device);
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   if (m->alibi) (void)hipFree(m->alibi);
+  quant_release(m);
   free_scratch(m);
   if (m->warena) (void)hipFree(m->warena);
   if (m->kcache && !m->borrowed) (void)hipFree(m->kcache);
@@ -1415,9 +1523,13 @@ int vsim_model_randomize(vsim_model *m, uint64_t seed, float stddev) {
 // (ne[0] = the inner dimension K, ne[1] = rows), its type the expected one, no tensor missing.
 // F32 / F16 weight files (f16 = 0 / 1, vsim.cpp:179-190) take the reference's F32 / F16 mul_mat,
 // which is not this library's path: they are refused with that reason.
-int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int layer_begin, int layer_end,
-                         vsim_model **out) {
+// With VSIM_LOAD_QUANTIZE (vsim_model_load_file_ex) the converters' F32 / F16 files load too: a
+// 2-D record whose slot is a Q4_0 matrix may have ftype 0 or 1 and streams through the staging
+// buffers into k_quantize_w (quantize_into_slot); every check and message is the plain loader's.
+static int load_file_impl(const char *path, int arch, int n_ctx, int device, int layer_begin, int layer_end, int flags,
+                          vsim_model **out) {
   if (!path || !out) { set_error("load: null argument"); return VSIM_EINVAL; }
+  const bool qz = (flags & VSIM_LOAD_QUANTIZE) != 0;
   std::ifstream f(path, std::ios::binary);
   if (!f) { set_error(std::string("load: cannot open ") + path); return VSIM_EFILE; }
   auto rd = [&](void *p, size_t n) { f.read((char *)p, n); return (size_t)f.gcount() == n; };
@@ -1440,10 +1552,10 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
   if (!ok) return bad("truncated header");
   if (hp.n_vocab <= 0 || hp.n_embd <= 0 || hp.n_head <= 0 || hp.n_layer <= 0 || hp.n_rot < 0)
     return bad("header values out of range");
-  if (ftype == 0 || ftype == 1)
+  if (!qz && (ftype == 0 || ftype == 1))
     return bad("F32 / F16 weight files take the reference's F32 / F16 mul_mat (vsim.cpp:179-190); this library "
                "runs the Q4_0 path: quantize the file to Q4_0 (f16 == 2) first");
-  if (ftype != 2) return bad("only Q4_0 (f16 == 2) files are supported");
+  if (ftype != 2 && !(qz && (ftype == 0 || ftype == 1))) return bad("only Q4_0 (f16 == 2) files are supported");
   int32_t nv = hp.n_vocab;
   if (arch == VSIM_ARCH_GPTJ && !rd(&nv, 4)) return bad("truncated vocab count");
   if (nv < 0 || nv > (1 << 24)) return bad("vocab count out of range");
@@ -1485,16 +1597,18 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
     }
     std::string name(ln, 0);
     if (!rd(&name[0], ln)) return fail_load("truncated tensor name");
-    if (ft != 0 && ft != 2) return fail_load("unsupported tensor type in " + name);
+    if (ft != 0 && ft != 2 && !(qz && ft == 1)) return fail_load("unsupported tensor type in " + name);
     if (ft == 2 && dims[0] % QK) return fail_load("Q4_0 tensor " + name + " with ne[0] not a multiple of 32");
-    const size_t nbytes = ft == 0 ? ne * 4 : ne / QK * QBYTES;
+    const size_t nbytes = ft == 0 ? ne * 4 : ft == 1 ? ne * 2 : ne / QK * QBYTES;
     // the tensor as the whole model's graph expects it (BLOOM's fused query_key_value: the
     // slot of its first row block, three times the rows)
     const bool fused = full.find(name) == full.end() && full.find(name + "/q") != full.end();
     auto fit = full.find(fused ? name + "/q" : name);
     if (fit == full.end()) return fail_load("unknown tensor " + name);
     const Slot &sl = fit->second;
-    if ((sl.kind == KQ4) != (ft == 2)) return fail_load("type mismatch " + name);
+    // a Q4_0 matrix arrives as Q4_0, or, when quantizing, as the F32 / F16 matrix it is made from
+    const bool from_src = qz && sl.kind == KQ4 && nd == 2 && ft != 2;
+    if (!from_src && (sl.kind == KQ4) != (ft == 2)) return fail_load("type mismatch " + name);
     const int want_rows = sl.kind == KQ4 ? sl.rows * (fused ? 3 : 1) : 1;
     if (dims[0] != sl.k || (nd == 2 ? dims[1] : 1) != want_rows) {
       char msg[256];
@@ -1507,6 +1621,20 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
       if (!f) return fail_load("truncated tensor " + name);
       continue;
     }
+    if (from_src) {  // the record's rows stream into the slot (BLOOM's fused one: q | k | v in turn)
+      if (hipSetDevice(m->device) != hipSuccess) return fail_load("cannot select the device");
+      for (int part = 0; part < (fused ? 3 : 1); ++part) {
+        Slot &dst = m->slots.find(fused ? name + QKV_PARTS[part] : name)->second;
+        const int rc = quantize_into_slot(m, dst, ft == 1 ? VSIM_SRC_F16 : VSIM_SRC_F32,
+                                          [&](void *p, size_t n) { return rd(p, n); });
+        if (rc == QUANT_SHORT) return fail_load("truncated tensor " + name);
+        if (rc) {
+          vsim_model_free(m);
+          return rc;
+        }
+      }
+      continue;
+    }
     buf.resize(nbytes);
     if (!rd(buf.data(), nbytes)) return fail_load("truncated tensor " + name);
     if (int rc = vsim_model_set_tensor(m, name.c_str(), buf.data(), nbytes)) {
@@ -1516,8 +1644,59 @@ int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int 
   }
   for (auto &kv : m->slots)
     if (!kv.second.loaded) return fail_load("tensor missing from file: " + kv.first);
+  quant_release(m);  // the staging buffers are not needed once the file is in
   *out = m;
   return VSIM_OK;
+}
+
+int vsim_model_load_file(const char *path, int arch, int n_ctx, int device, int layer_begin, int layer_end,
+                         vsim_model **out) {
+  return load_file_impl(path, arch, n_ctx, device, layer_begin, layer_end, 0, out);
+}
+
+int vsim_model_load_file_ex(const char *path, int arch, int n_ctx, int device, int layer_begin, int layer_end,
+                            int flags, vsim_model **out) {
+  if (flags & ~VSIM_LOAD_QUANTIZE) { set_error("load: unknown flag"); return VSIM_EINVAL; }
+  return load_file_impl(path, arch, n_ctx, device, layer_begin, layer_end, flags, out);
+}
+
+int vsim_quantize_set_chunk_rows(int rows) { return g_quant_chunk_rows.exchange(rows > 0 ? rows : 0); }
+
+int vsim_model_set_tensor_src(vsim_model *m, const char *name, const void *host, size_t nbytes, int src_type) {
+  if (!m || !name || !host) { set_error("set_tensor_src: null argument"); return VSIM_EINVAL; }
+  if (src_type != VSIM_SRC_F32 && src_type != VSIM_SRC_F16) {
+    set_error("set_tensor_src: src_type must be VSIM_SRC_F32 or VSIM_SRC_F16");
+    return VSIM_EINVAL;
+  }
+  if (m->borrowed) { set_error("set_tensor_src: the weights belong to the graph executor"); return VSIM_EINVAL; }
+  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks, q | k | v
+    if (nbytes % 3 != 0) { set_error("set_tensor_src: fused qkv size"); return VSIM_EINVAL; }
+    for (int i = 0; i < 3; ++i)
+      RC(vsim_model_set_tensor_src(m, (n + QKV_PARTS[i]).c_str(), (const uint8_t *)host + i * (nbytes / 3), nbytes / 3,
+                                   src_type));
+    return VSIM_OK;
+  }
+  auto it = m->slots.find(name);
+  if (it == m->slots.end()) { set_error(std::string("set_tensor_src: unknown tensor ") + name); return VSIM_EINVAL; }
+  Slot &s = it->second;
+  if (s.kind == KF32) {  // 1-D tensors stay F32: the existing path
+    if (src_type != VSIM_SRC_F32) {
+      set_error(std::string("set_tensor_src: ") + name + " is an F32 vector");
+      return VSIM_EINVAL;
+    }
+    return vsim_model_set_tensor(m, name, host, nbytes);
+  }
+  if (nbytes != (size_t)s.rows * s.k * (src_type == VSIM_SRC_F16 ? 2 : 4)) {
+    set_error(std::string("set_tensor_src: wrong size for ") + name);
+    return VSIM_EINVAL;
+  }
+  VSIM_HIP(hipSetDevice(m->device));
+  const uint8_t *src = (const uint8_t *)host;
+  return quantize_into_slot(m, s, src_type, [&](void *p, size_t n) {
+    memcpy(p, src, n);
+    src += n;
+    return true;
+  });
 }
 
 int vsim_model_set_mode(vsim_model *m, int mode) {

@@ -46,7 +46,12 @@ EXPORTS = [
     "vsim_model_debug_poison",
     "vsim_op_topk", "vsim_sampler_create", "vsim_sampler_accept", "vsim_sampler_pick", "vsim_sampler_sample_host",
     "vsim_sampler_stats", "vsim_sampler_free", "vsim_model_eval_sample", "vsim_model_generate_sampled",
+    "vsim_op_q4_quantize_w", "vsim_model_load_file_ex", "vsim_model_set_tensor_src", "vsim_quantize_set_chunk_rows",
+    "vsim_quantize_file", "vsim_quantize_set_verbose",
 ]
+
+SRC_F32, SRC_F16 = 0, 1  # VSIM_SRC_*
+LOAD_QUANTIZE = 1        # VSIM_LOAD_QUANTIZE
 
 TOPK_MAX = 64      # VSIM_TOPK_MAX
 WINDOW_MAX = 1024  # VSIM_WINDOW_MAX
@@ -124,6 +129,11 @@ class FastTailArgs(ctypes.Structure):
                 ("vc", ctypes.c_void_p), ("n_past", ctypes.c_void_p), ("d", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("nchunk", ctypes.c_int32), ("scale", ctypes.c_float), ("part", ctypes.c_void_p),
                 ("hcnt", ctypes.c_void_p), ("oq", ctypes.c_void_p)]
+
+
+class QuantizeStats(ctypes.Structure):
+    _fields_ = [("hist", ctypes.c_uint64 * 16), ("bytes_in", ctypes.c_uint64), ("bytes_out", ctypes.c_uint64),
+                ("n_quantized", ctypes.c_int32), ("n_copied", ctypes.c_int32)]
 
 
 class HParams(ctypes.Structure):
@@ -228,6 +238,12 @@ def lib():
     L.vsim_model_eval_sample.argtypes = [vp, vp, ci, ctypes.c_int32, i32p]
     L.vsim_model_generate_sampled.argtypes = [vp, vp, ci, ctypes.c_int32, ci, ctypes.c_int32, i32p,
                                               ctypes.POINTER(ci)]
+    L.vsim_op_q4_quantize_w.argtypes = [vp, ci, ci, ci, vp, ci, ci, vp, vp, vp]
+    L.vsim_model_load_file_ex.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+    L.vsim_model_set_tensor_src.argtypes = [vp, ctypes.c_char_p, vp, sz, ci]
+    L.vsim_quantize_set_chunk_rows.argtypes = [ci]
+    L.vsim_quantize_file.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.POINTER(QuantizeStats)]
+    L.vsim_quantize_set_verbose.argtypes = [ci]
     _lib = L
     return L
 
@@ -249,6 +265,29 @@ def ptr(t) -> int:
 
 def q4_bytes(rows: int, k: int) -> int:
     return int(lib().vsim_q4_bytes(rows, k))
+
+
+def quantize_w(x, src_type, rows, k, w=None, w_rows=0, row0=0, aos=None, hist=None, stream=None):
+    """vsim_op_q4_quantize_w on device buffers (torch tensors): x [rows][k] float32 (SRC_F32) or
+    float16 (SRC_F16); w a W4T32 weight of w_rows rows of which rows [row0, row0 + rows) are written,
+    aos the chunk's 20-byte blocks, hist 16 uint64 counters the caller zeroed (each may be None,
+    but not both w and aos).  Enqueued on `stream`, not synchronized."""
+    check(lib().vsim_op_q4_quantize_w(ptr(x), src_type, rows, k, ptr(w), w_rows, row0, ptr(aos), ptr(hist), stream),
+          "q4_quantize_w")
+
+
+def quantize_set_chunk_rows(rows: int) -> int:
+    """Rows per staging chunk of the quantizing loader (0 = default); returns the previous value."""
+    return int(lib().vsim_quantize_set_chunk_rows(int(rows)))
+
+
+def quantize_file(src: str, dst: str, arch: int, device: int = 0) -> dict:
+    """vsim_quantize_file: an F32 / F16 ggml file to Q4_0, on GPU `device` or (device = -1) on the
+    host; returns the statistics."""
+    st = QuantizeStats()
+    check(lib().vsim_quantize_file(src.encode(), dst.encode(), arch, device, ctypes.byref(st)), f"quantize {src}")
+    return {"hist": [int(v) for v in st.hist], "bytes_in": int(st.bytes_in), "bytes_out": int(st.bytes_out),
+            "n_quantized": int(st.n_quantized), "n_copied": int(st.n_copied)}
 
 
 class Sampler:
@@ -352,10 +391,12 @@ class Model:
         self.last = self.layer_end == hp.n_layer
 
     @classmethod
-    def load(cls, path, arch, n_ctx=512, device=0, layer_begin=0, layer_end=-1):
+    def load(cls, path, arch, n_ctx=512, device=0, layer_begin=0, layer_end=-1, quantize=False):
+        """quantize=True also takes the converters' F32 / F16 files, quantized on the device as they
+        load (vsim_model_load_file_ex with VSIM_LOAD_QUANTIZE)."""
         h = ctypes.c_void_p()
-        check(lib().vsim_model_load_file(path.encode(), arch, n_ctx, device, layer_begin, layer_end,
-                                         ctypes.byref(h)), f"load {path}")
+        check(lib().vsim_model_load_file_ex(path.encode(), arch, n_ctx, device, layer_begin, layer_end,
+                                            LOAD_QUANTIZE if quantize else 0, ctypes.byref(h)), f"load {path}")
         return cls(h, arch)
 
     @classmethod
@@ -368,6 +409,14 @@ class Model:
 
     def randomize(self, seed=0, std=0.02):
         check(lib().vsim_model_randomize(self.h, seed, std), "randomize")
+
+    def set_tensor_src(self, name: str, values: np.ndarray):
+        """Upload one tensor as float32 / float16 values; a matrix is quantized into its Q4_0 slot."""
+        v = np.ascontiguousarray(values)
+        if v.dtype not in (np.float32, np.float16):
+            raise TypeError("set_tensor_src takes float32 or float16 values")
+        check(lib().vsim_model_set_tensor_src(self.h, name.encode(), ptr(v), v.nbytes,
+                                              SRC_F16 if v.dtype == np.float16 else SRC_F32), f"set_tensor_src {name}")
 
     def get_tensor(self, name: str, nbytes: int) -> np.ndarray:
         """One tensor in the ggml file's format (Q4_0 AoS blocks / F32), as raw bytes."""

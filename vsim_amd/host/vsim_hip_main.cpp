@@ -7,7 +7,8 @@
 // prints "logits: %.8f ..." rows.  The model runs in libvsim_hip.so (device resident);
 // this file is host control only: the sampler too is the library's (vsim_sampler_*).
 // Extra flags: --device N, --mode exact|fast, --n_ctx N (reference: fixed 512,
-// vsim.cpp:758), --no-graph, --sampler host|device.
+// vsim.cpp:758), --no-graph, --sampler host|device, --quantize (load an F32 / F16 file as the
+// converters write it, quantized to Q4_0 on the device while it loads).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -40,6 +41,7 @@ struct Params {
   int n_ctx = 512;
   bool graph = true;
   bool device_sampler = true;
+  bool quantize = false;
 };
 
 void usage(const char *argv0, const Params &p) {
@@ -58,6 +60,7 @@ void usage(const char *argv0, const Params &p) {
   fprintf(stderr, "  --mode exact|fast     exact = bit-identical to the reference (default)\n");
   fprintf(stderr, "  --n_ctx N             context length (default 512, as the reference)\n");
   fprintf(stderr, "  --no-graph            launch every kernel eagerly\n");
+  fprintf(stderr, "  --quantize            the model file is F32 / F16: quantize it to Q4_0 on the GPU while loading\n");
   fprintf(stderr, "  --sampler host|device device = penalty, temperature and top-k on the GPU (default);\n");
   fprintf(stderr, "                        host = the logits row is copied out and sampled on the CPU\n");
 }
@@ -89,6 +92,7 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "--mode") p.mode = std::string(next()) == "fast" ? VSIM_MODE_FAST : VSIM_MODE_EXACT;
     else if (a == "--n_ctx") p.n_ctx = std::stoi(next());
     else if (a == "--no-graph") p.graph = false;
+    else if (a == "--quantize") p.quantize = true;
     else if (a == "--sampler") {
       const std::string v = next();
       if (v != "host" && v != "device") {
@@ -165,7 +169,11 @@ int run(const Params &params, int arch) {
   }
   vsim_model *model = nullptr;
   printf("%s: loading model from '%s' - please wait ...\n", __func__, params.model.c_str());
-  if (vsim_model_load_file(params.model.c_str(), arch, params.n_ctx, params.device, 0, -1, &model) != VSIM_OK) {
+  const int load_rc = params.quantize ? vsim_model_load_file_ex(params.model.c_str(), arch, params.n_ctx, params.device,
+                                                                0, -1, VSIM_LOAD_QUANTIZE, &model)
+                                      : vsim_model_load_file(params.model.c_str(), arch, params.n_ctx, params.device,
+                                                             0, -1, &model);
+  if (load_rc != VSIM_OK) {
     fprintf(stderr, "%s: failed to load model from '%s': %s\n", __func__, params.model.c_str(), vsim_last_error());
     return 1;
   }

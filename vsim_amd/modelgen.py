@@ -40,6 +40,38 @@ def quantize_q4_0(x: np.ndarray) -> np.ndarray:
     return out.reshape(-1)
 
 
+def quantize_q4_0_w(x: np.ndarray, nan_as_max: bool = False):
+    """The model quantizer, ggml_quantize_q4_0 (utils.cpp:425-482), over every 32-block of float32
+    values; returns (uint8 bytes, 16-bin histogram of the codes).
+
+    quantize_q4_0's arithmetic with the one difference of the weight path: amax is taken with
+    std::max(amax, fabsf(v)), which IGNORES a NaN (the block keeps the d of its other values),
+    where quantize_row_q4_0's MAX macro lets a NaN replace the running maximum (nan_as_max=True
+    restates that, for the tests that show the two apart).  (int8_t)round(v) is the x86 cast:
+    inf, NaN and anything beyond int32 give 0, so such elements get code 8.
+    """
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, QK)
+    a = np.abs(x)
+    if nan_as_max:  # MAX(a, b) = a > b ? a : b, left to right from 0
+        amax = np.zeros(x.shape[0], np.float32)
+        for l in range(QK):
+            amax = np.where(amax > a[:, l], amax, a[:, l])
+    else:
+        amax = np.fmax.reduce(a, axis=1, initial=np.float32(0.0)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        d = (amax / np.float32(7.0)).astype(np.float32)
+        idv = np.where(d != 0, np.float32(1.0) / d, np.float32(0.0)).astype(np.float32)
+        v = (x * idv[:, None]).astype(np.float32).astype(np.float64)
+        r = np.where(v >= 0, np.floor(v + 0.5), np.ceil(v - 0.5))
+        ok = np.isfinite(r) & (np.abs(r) < 2147483648.0)
+    i8 = np.where(ok, r, 0.0).astype(np.int64).astype(np.int8)  # cvttsd2si, then the low byte
+    q = ((i8.astype(np.int64) + 8) & 0xF).astype(np.uint8)
+    out = np.empty((x.shape[0], QBYTES), dtype=np.uint8)
+    out[:, :4] = d.view(np.uint8).reshape(-1, 4)
+    out[:, 4:] = q[:, 0::2] | (q[:, 1::2] << 4)
+    return out.reshape(-1), np.bincount(q.reshape(-1), minlength=16).astype(np.uint64)
+
+
 def dequantize_q4_0(b: np.ndarray, k: int) -> np.ndarray:
     """dequantize_row_q4_0 (ggml.c:301-334) for rows of k weights."""
     blk = np.asarray(b, dtype=np.uint8).reshape(-1, QBYTES)
@@ -61,7 +93,7 @@ class HParams:
     n_layer: int
     n_rot: int
     use_parallel_residual: int = 1
-    ftype: int = 2  # 2 = Q4_0
+    ftype: int = 2  # 2 = Q4_0; 0 / 1 = the converters' F32 / F16 files (2-D weights unquantized)
 
     @property
     def n_ff(self) -> int:
@@ -163,41 +195,72 @@ def tensor_specs(arch: str, hp: HParams):
     return s
 
 
-def gen_tensors(arch: str, hp: HParams, seed: int = 0, std: float = 0.02):
-    """Yield (name, ne, ftype, raw bytes) in file order."""
+def gen_tensors(arch: str, hp: HParams, seed: int = 0, std: float = 0.02, quantized: bool = False):
+    """Yield (name, ne, ftype, raw bytes) in file order.
+
+    hp.ftype 2: 2-D weights as Q4_0.  hp.ftype 1 / 0: as F16 / F32, the values rounded to F16
+    first in both cases (what convert_*_to_ggml.py writes from an fp16 checkpoint); with
+    quantized=True, those same weights as the model quantizer turns them into Q4_0.  1-D tensors
+    are F32 throughout, as the converters write them.
+    """
     rng = np.random.Generator(np.random.PCG64(seed))
     for name, ne, kind in tensor_specs(arch, hp):
         n = int(np.prod(ne))
         vals = rng.standard_normal(n, dtype=np.float32) * np.float32(std)
         if kind == "w":
             vals = vals + np.float32(1.0)
-        if kind == "q":
+        if kind == "q" and hp.ftype == 2:
             yield name, ne, 2, quantize_q4_0(vals.astype(np.float32)).tobytes()
+        elif kind == "q":
+            v16 = vals.astype(np.float16)
+            if quantized:
+                yield name, ne, 2, quantize_q4_0_w(v16.astype(np.float32))[0].tobytes()
+            elif hp.ftype == 1:
+                yield name, ne, 1, v16.tobytes()
+            else:
+                yield name, ne, 0, v16.astype(np.float32).tobytes()
         else:
             yield name, ne, 0, vals.astype(np.float32).tobytes()
 
 
+def expected_q4_0_image(arch: str, hp: HParams, seed: int = 0, std: float = 0.02) -> bytes:
+    """The Q4_0 file the quantizer must make of write_model(path, arch, hp, seed, std) with
+    hp.ftype 0 or 1: same header (f16 = 2), vocab and 1-D records, every 2-D weight requantized
+    with quantize_q4_0_w."""
+    import io
+    import dataclasses
+    if hp.ftype not in (0, 1):
+        raise ValueError("expected_q4_0_image: hp.ftype must be 0 or 1")
+    f = io.BytesIO()
+    _write(f, arch, dataclasses.replace(hp, ftype=2), gen_tensors(arch, hp, seed, std, quantized=True))
+    return f.getvalue()
+
+
 def write_model(path: str, arch: str, hp: HParams, seed: int = 0, std: float = 0.02) -> None:
     with open(path, "wb") as f:
-        f.write(struct.pack("<I", 0x67676D6C))
-        if arch == "gptneox":
-            f.write(struct.pack("<7i", hp.n_vocab, hp.n_embd, hp.n_head, hp.n_layer, hp.n_rot,
-                                hp.use_parallel_residual, hp.ftype))
-        elif arch == "bloom":  # convert_bloom_to_ggml.py:79-85 (multiple_of = 1)
-            f.write(struct.pack("<6i", hp.n_vocab, hp.n_embd, 1, hp.n_head, hp.n_layer, hp.ftype))
-        else:
-            f.write(struct.pack("<6i", hp.n_vocab, hp.n_embd, hp.n_head, hp.n_layer, hp.n_rot, hp.ftype))
-            f.write(struct.pack("<i", hp.n_vocab))
-        for i in range(hp.n_vocab):
-            tok = f"t{i}".encode()
-            f.write(struct.pack("<I", len(tok)))
-            f.write(tok)
-        for name, ne, ftype, raw in gen_tensors(arch, hp, seed, std):
-            nb = name.encode()
-            f.write(struct.pack("<3i", len(ne), len(nb), ftype))
-            f.write(struct.pack(f"<{len(ne)}i", *ne))
-            f.write(nb)
-            f.write(raw)
+        _write(f, arch, hp, gen_tensors(arch, hp, seed, std))
+
+
+def _write(f, arch: str, hp: HParams, tensors) -> None:
+    f.write(struct.pack("<I", 0x67676D6C))
+    if arch == "gptneox":
+        f.write(struct.pack("<7i", hp.n_vocab, hp.n_embd, hp.n_head, hp.n_layer, hp.n_rot,
+                            hp.use_parallel_residual, hp.ftype))
+    elif arch == "bloom":  # convert_bloom_to_ggml.py:79-85 (multiple_of = 1)
+        f.write(struct.pack("<6i", hp.n_vocab, hp.n_embd, 1, hp.n_head, hp.n_layer, hp.ftype))
+    else:
+        f.write(struct.pack("<6i", hp.n_vocab, hp.n_embd, hp.n_head, hp.n_layer, hp.n_rot, hp.ftype))
+        f.write(struct.pack("<i", hp.n_vocab))
+    for i in range(hp.n_vocab):
+        tok = f"t{i}".encode()
+        f.write(struct.pack("<I", len(tok)))
+        f.write(tok)
+    for name, ne, ftype, raw in tensors:
+        nb = name.encode()
+        f.write(struct.pack("<3i", len(ne), len(nb), ftype))
+        f.write(struct.pack(f"<{len(ne)}i", *ne))
+        f.write(nb)
+        f.write(raw)
 
 
 def read_model(path: str, arch: str):
@@ -237,7 +300,7 @@ def read_model(path: str, arch: str):
         name = buf[off:off + ln].decode()
         off += ln
         n = int(np.prod(ne))
-        nbytes = n * 4 if ft == 0 else n // QK * QBYTES
+        nbytes = n * 4 if ft == 0 else n * 2 if ft == 1 else n // QK * QBYTES
         tensors[name] = (ne, ft, buf[off:off + nbytes])
         off += nbytes
     return hp, tensors
