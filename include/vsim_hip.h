@@ -237,6 +237,27 @@ int vsim_op_argmax(const float *x, int n, int32_t *out, void *stream);
 #define VSIM_WINDOW_MAX 1024
 int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale, double repeat_penalty, int k,
                  double *val, int32_t *id, void *stream);
+/* Scoring: the log-probability a logits row gives one token, and the row's greedy id, for R rows
+ * x[R][V] (f32, row stride V, so any 4-byte alignment) in one launch (k_score_rows, score.hip).
+ * Per row i, with m the row's maximum (a float, exact) and t = target[i]:
+ *   s = sum_j exp((double)x[i][j] - (double)m)   in double
+ *   lse = (double)m + log(s)
+ *   logprob[i] = (double)x[i][t] - lse
+ *   argmax[i]  = vsim_op_argmax's id (first maximum, -0.0 == +0.0, the first NaN if any)
+ * t == -1 means "no target": logprob[i] = 0.0, argmax[i] is still written.  Ids outside [-1, V) are
+ * the caller's bug at this level; the kernel treats them as -1 instead of reading out of bounds.
+ * Order rule: one workgroup per row; thread k of 1024 adds the terms j = k, k + 1024, .. in that
+ * order, the partials are added by one fixed tree.  A row's outputs therefore depend on that
+ * row's contents only -- not on R, on the rows beside it in the launch, or on the run: the same
+ * row gives the same bits every time.  (Another summation order, e.g. a host reference's,
+ * differs by at most (V - 1) 2^-53 relative in s.)
+ * NaN / Inf rule: -inf entries contribute 0.  A row holding a NaN, or whose maximum is +inf or
+ * -inf, has logprob = NaN (and argmax by the rule above); the kernel terminates on every input.
+ * All pointers are device pointers; logprob or argmax may be NULL (not both), target may be NULL
+ * (all -1).  Enqueued on stream, not synchronized.  VSIM_EINVAL for V < 1, R < 0 or both outputs
+ * NULL; R == 0 is a no-op. */
+int vsim_op_logprob(const float *x, int V, int R, const int32_t *target, double *logprob, int32_t *argmax,
+                    void *stream);
 /* scale -> diag_mask_inf(n_past) -> soft_max over p[nz][nr][nc], in place */
 int vsim_op_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, void *stream);
 /* style 0 = GPT-NeoX rotate-half (ggml.c:6086), 1 = GPT-J pairs (ggml.c:5919);
@@ -446,6 +467,35 @@ int vsim_model_hparams(const vsim_model *m, vsim_hparams *hp, int *n_ctx, int *l
  * the last row of logits to `logits` (host, n_vocab floats) if non-NULL. */
 int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in,
                     float *resid_out, float *logits);
+/* Scoring eval: vsim_model_eval's N-token prompt pass, then the head over ALL N rows instead of
+ * the last one -- per position i the log-probability of targets[i] and the greedy id
+ * (vsim_op_logprob's definition, order rule and NaN / Inf rule), without the logits leaving the
+ * device.  This is how a numeric path's loss is measured: score one text in exact and in fast
+ * mode, or from an F16-quantized and a Q4_0 file, and compare.
+ *   targets, logprob, argmax   host arrays of N (targets NULL: all -1; logprob / argmax may be
+ *                              NULL).  targets[i] is usually tokens[i + 1]; -1 scores nothing.
+ *   logits_all                 optional host buffer [N][n_vocab] receiving every logits row (NULL
+ *                              in normal use: tests, and callers who want every row).
+ * Valid on the stage that owns the head: a whole model reads `tokens`, a last pipeline stage
+ * `resid_in` (device, [N][n_embd]); a stage without the head returns VSIM_EINVAL (earlier stages
+ * keep using vsim_model_eval with resid_out).  VSIM_EINVAL too for a target outside
+ * [-1, n_vocab) and for vsim_model_eval's n_past / N range errors; VSIM_ESPIN as vsim_model_eval.
+ * The embedding and the layers are vsim_model_eval's prompt path in the model's current mode for
+ * every N (N == 1 included: not the captured decode step), and the KV cache ends in the state
+ * vsim_model_eval(m, n_past, tokens, N, ..) leaves, so windows chain and a decode step may follow.
+ * The head runs over chunks of C rows -- final LayerNorm, lm_head product, k_score_rows, the
+ * optional copy-out -- through a [C][n_vocab] f32 scratch allocated on the first scoring call;
+ * C = 64 MiB / (4 n_vocab) clamped to 8..256 (vsim_score_set_chunk_rows).  One copy of N doubles
+ * and N ints leaves the device at the end.
+ * Exact mode: every row of logits_all, hence every argmax, is bit for bit the logits row
+ * vsim_model_eval gives for the prefix ending at that position (the reference's), whatever C is.
+ * Fast mode: the chunk's row count picks the lm_head kernel (256 or more rows: the 256-tile fp16
+ * MFMA GEMM; 8 or more: the small-tile one; fewer: quantize + GEMV), so bits may depend on C. */
+int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in,
+                          const int32_t *targets, double *logprob, int32_t *argmax, float *logits_all);
+/* Rows per head chunk of vsim_model_eval_score, process-wide: 0 = the default, other values are
+ * capped at 256.  Returns the previous value.  For tests: many ragged chunks on tiny models. */
+int vsim_score_set_chunk_rows(int rows);
 /* Greedy single-token decode step of a whole-model stage: eval of `token` at n_past, then
  * the argmax of the logits on the device (numpy.argmax conventions: first maximum, first
  * NaN); only the token id leaves the device.  The reference's loop samples on the host

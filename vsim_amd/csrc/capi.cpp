@@ -164,6 +164,9 @@ int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale
   }
   return launch_topk(x, n, nullptr, win, nw, scale, repeat_penalty, k, val, id, ws, (hipStream_t)stream);
 }
+int vsim_op_logprob(const float *x, int V, int R, const int32_t *target, double *logprob, int32_t *argmax, void *stream) {
+  return launch_score_rows(x, V, R, target, logprob, argmax, (hipStream_t)stream);
+}
 int vsim_op_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, void *stream) {
   return launch_attn_softmax(p, nc, nr, nz, n_past, scale, (hipStream_t)stream);
 }

@@ -327,6 +327,11 @@ constexpr int TOPK_MAX_WG = 64;
 constexpr size_t TOPK_WS_BYTES = 256 + (size_t)TOPK_MAX_WG * 64 * (sizeof(unsigned long long) + sizeof(uint32_t));
 int launch_topk(const float *x, int n, const TopkParams *pb, const int32_t *win, int nw, double scale, double penalty,
                 int k, double *val, int32_t *id, void *ws, hipStream_t s);
+// Per-row log-probability and greedy id of R logit rows x[R][V] (score.hip, vsim_op_logprob):
+// one workgroup per row, a fixed summation order per row; target / logprob / argmax may be null
+// (not both outputs)
+int launch_score_rows(const float *x, int V, int R, const int32_t *target, double *logprob, int32_t *argmax,
+                      hipStream_t s);
 int launch_gemm_q4_f16(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
 // fast-mode prompt batches (n >= GEMM_MIN_N): activation rows quantized (optionally after
 // bias + GELU) straight to the GEMM's fp16 operand x16 [n][K], and the GEMM on it

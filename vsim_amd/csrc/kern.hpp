@@ -53,6 +53,18 @@ __device__ __forceinline__ void quantize_block(const float *v, uint8_t *qs_out, 
   }
 }
 
+// ------------------------------------------------------------------ greedy key
+// A logit and its index as one 64-bit key whose unsigned order is numpy.argmax's: the value's
+// bits mapped to an unsigned order (NaN -> all ones, -0.0 -> +0.0) above ~index, so the largest
+// key belongs to the first maximum, or to the first NaN (k_argmax, k_score_rows).
+__device__ __forceinline__ unsigned long long am_key(float v, int i) {
+  uint32_t u = __float_as_uint(v);
+  if (v != v) u = 0xFFFFFFFFu;
+  else if (v == 0.0f) u = 0x80000000u;
+  else u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (uint32_t)i);
+}
+
 // ------------------------------------------------------------------ pair products
 // The reference's per-byte term (imax.c:1219-1226): f0 = d0*(lo-8), f1 = d0*(hi-8),
 // p = f0*f2 + f1*f3, every product and the sum rounded separately (no FMA).  The nibble

@@ -141,6 +141,13 @@ struct vsim_model {
   void *pf_scratch = nullptr;  // fast prefill: fp16 K / V^T copies (attn_prefill.hip)
   void *pf_x16 = nullptr;      // fast prefill: fp16 GEMM operands, [n_max][E] then [n_max][4E]
   size_t pf_bytes = 0;
+  // scoring (vsim_model_eval_score), allocated on the first scoring call (ensure_score_scratch):
+  // one head chunk's logits [score_rows][n_vocab], the targets (pinned, device) and the results
+  // (device, pinned: n_max doubles, then n_max ints)
+  int score_rows = 0;
+  float *score_x = nullptr;
+  int32_t *score_tgt = nullptr, *score_tgt_host = nullptr;
+  void *score_out = nullptr, *score_out_host = nullptr;
 
   // graph executor's fast path (graph.cpp): weights and KV cache borrowed from its device
   // mirrors (not freed here), the KQV key grouping of the caller's thread count and the
@@ -187,7 +194,8 @@ int E_(const vsim_model *m) { return m->hp.n_embd; }
 // ---------------------------------------------------------------- scratch
 // Every scratch allocation for n tokens, in allocation order: where the pointer lives, its
 // bytes (0: not allocated at this n), and how it is allocated and treated.
-enum { S_PINNED = 1, S_ZERO = 2, S_POISON = 4 };  // pinned host memory; zero-filled; NaN-filled by debug_poison
+// pinned host memory; zero-filled; NaN-filled by debug_poison; scoring's (0 bytes until score_rows is set)
+enum { S_PINNED = 1, S_ZERO = 2, S_POISON = 4, S_SCORE = 8 };
 struct ScratchBuf {
   void **p;
   size_t bytes;
@@ -251,6 +259,12 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->fast_ffp, 8 * E * f);
   add(&m->pf_x16, n >= (size_t)GEMM_MIN_N ? n * (E + F) * sizeof(uint16_t) : 0, S_POISON);
   add(&m->fast_part, H * nch * (d + 2) * f, S_ZERO);  // finite stale values
+  const size_t sn = m->score_rows ? n : 0, so = sizeof(double) + sizeof(int32_t);
+  add(&m->score_x, (size_t)m->score_rows * V * f, S_POISON | S_SCORE);
+  add(&m->score_tgt, sn * sizeof(int32_t), S_SCORE);
+  add(&m->score_tgt_host, sn * sizeof(int32_t), S_PINNED | S_SCORE);
+  add(&m->score_out, sn * so, S_SCORE);
+  add(&m->score_out_host, sn * so, S_PINNED | S_SCORE);
   return t;
 }
 
@@ -289,6 +303,34 @@ int ensure_scratch(vsim_model *m, int N) {
   }
   carve_lnt(m);
   m->n_max = n;
+  return VSIM_OK;
+}
+
+// Scoring's buffers for head chunks of `rows` rows, allocated on the first scoring call (and
+// again when a larger chunk is asked for); from then on they follow the scratch's size like
+// every other entry of the table.  After ensure_scratch.
+int ensure_score_scratch(vsim_model *m, int rows) {
+  if (rows <= m->score_rows) return VSIM_OK;
+  VSIM_HIP(hipStreamSynchronize(m->stream));
+  auto release = [&] {
+    for (const ScratchBuf &b : scratch_table(m, m->n_max)) {
+      if (!(b.flags & S_SCORE) || !*b.p) continue;
+      (void)(b.flags & S_PINNED ? hipHostFree(*b.p) : hipFree(*b.p));
+      *b.p = nullptr;
+    }
+  };
+  release();
+  m->score_rows = rows;
+  for (const ScratchBuf &b : scratch_table(m, m->n_max)) {
+    if (!(b.flags & S_SCORE) || !b.bytes) continue;
+    const hipError_t e = b.flags & S_PINNED ? hipHostMalloc(b.p, b.bytes, hipHostMallocDefault) : hipMalloc(b.p, b.bytes);
+    if (e != hipSuccess) {
+      *b.p = nullptr;
+      release();
+      m->score_rows = 0;
+      return hip_fail(e, "score scratch");
+    }
+  }
   return VSIM_OK;
 }
 
@@ -549,10 +591,12 @@ double w4_algo_bytes(const W4 &w) { return (double)w.rows * w.k / QK * QBYTES; }
 // prompt batches): the activation is already the GEMM's fp16 operand (launch_act_quant_f16).
 // gq (fc_in of a long prompt): bias gq_bias + GELU + quantize of the product straight into the
 // next GEMM's fp16 operand gq, in the GEMM's epilogue; epi: RoPE or the residual join in the
-// epilogue (G2Epi); *fused tells the caller whether either ran.
+// epilogue (G2Epi); *fused tells the caller whether either ran.  what: the profile's name for the
+// product instead of the kernel's.
 int mm(vsim_model *m, const void *W, int M, int K, const float *x, int N, uint8_t *xq, float *xd, bool quantize,
        const float *bias, float *y, int &nk, const void *x16 = nullptr, void *gq = nullptr,
-       const float *gq_bias = nullptr, bool *fused = nullptr, const G2Epi *epi = nullptr) {
+       const float *gq_bias = nullptr, bool *fused = nullptr, const G2Epi *epi = nullptr,
+       const char *what = nullptr) {
   if (fused) *fused = false;
   if (quantize && !x16) {
     RC(launch_q4_quantize(x, K, N, xq, xd, m->stream));
@@ -564,14 +608,14 @@ int mm(vsim_model *m, const void *W, int M, int K, const float *x, int N, uint8_
     LAUNCH(m, nk,
            launch_gemm_q4_256(w4_view(W, M, K), x16, N, gelu ? gq_bias : bias, y, m->stream, gelu ? gq : nullptr,
                               gelu ? nullptr : epi),
-           "k_gemm_f16_256 (prompt)", (double)M * K / QK * QBYTES);
+           what ? what : "k_gemm_f16_256 (prompt)", (double)M * K / QK * QBYTES);
     if (fused) *fused = gelu || epi;
     return VSIM_OK;
   }
   LAUNCH(m, nk,
          x16 ? launch_gemm_f16x(w4_view(W, M, K), x16, N, bias, y, m->stream)
              : launch_q4_gemv(W, M, K, xq, xd, N, bias, y, m->mode, m->stream),
-         x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
+         what ? what : x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
          (double)M * K / QK * QBYTES);
   return VSIM_OK;
 }
@@ -1837,6 +1881,49 @@ int run_step(vsim_model *m, StepKind kind, bool graph, int &nk, bool want_logits
   return VSIM_OK;
 }
 
+// The general path up to the head (prompt batches; scoring at every N): the embedding of
+// `tokens` (first stage) or the residual from resid_in, then this stage's layers; the rows'
+// residual ends in inpL.  `who` prefixes the error messages.
+int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in, int &nk,
+                   const char *who) {
+  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+  hipStream_t s = m->stream;
+  if (m->first) {
+    if (!tokens) { set_error(std::string(who) + ": first stage needs tokens"); return VSIM_EINVAL; }
+    for (int i = 0; i < N; ++i) {
+      if (tokens[i] < 0 || tokens[i] >= V) { set_error(std::string(who) + ": token id out of range"); return VSIM_EINVAL; }
+      m->tok_host[i] = tokens[i];
+    }
+    VSIM_HIP(hipMemcpyAsync(m->tok_dev, m->tok_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (m->arch == VSIM_ARCH_BLOOM) {  // word embeddings + word_embeddings_layernorm
+      RC(launch_get_rows(m->wte, E, V, m->tok_dev, N, m->cur1, s));
+      RC(launch_norm(m->cur1, m->inpL, E, N, m->emb_w, m->emb_b, s));
+      nk += 2;
+    } else {
+      RC(launch_get_rows(m->wte, E, V, m->tok_dev, N, m->inpL, s));
+      ++nk;
+    }
+  } else {
+    if (!resid_in) { set_error(std::string(who) + ": non-first stage needs resid_in"); return VSIM_EINVAL; }
+    VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
+  }
+  for (int il = m->l0; il < m->l1; ++il) RC(run_layer(m, il, n_past, N, nk));
+  return VSIM_OK;
+}
+
+std::atomic<int> g_score_chunk_rows{0};  // vsim_score_set_chunk_rows (0: default)
+constexpr size_t SCORE_SCRATCH_BYTES = (size_t)64 << 20;
+constexpr int SCORE_MIN_ROWS = 8, SCORE_MAX_ROWS = 256;
+
+// rows per head chunk of a scoring eval: the [C][n_vocab] f32 scratch at or below 64 MiB, at
+// least 8 rows (the fp16 GEMM's minimum), at most 256 (one tile column of the long-prompt GEMM)
+int score_chunk_rows(const vsim_model *m) {
+  const int c = g_score_chunk_rows.load();
+  if (c > 0) return std::min(c, SCORE_MAX_ROWS);
+  const size_t fit = SCORE_SCRATCH_BYTES / ((size_t)m->hp.n_vocab * sizeof(float));
+  return (int)std::max<size_t>(SCORE_MIN_ROWS, std::min<size_t>(fit, SCORE_MAX_ROWS));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1997,26 +2084,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
     RC(run_step(m, STEP_LOGITS, m->graph_enabled && m->first && m->last, nk, logits != nullptr, resid_out));
   } else {
     // general path: prompt batches (N > 1)
-    if (m->first) {
-      if (!tokens) { set_error("eval: first stage needs tokens"); return VSIM_EINVAL; }
-      for (int i = 0; i < N; ++i) {
-        if (tokens[i] < 0 || tokens[i] >= V) { set_error("eval: token id out of range"); return VSIM_EINVAL; }
-        m->tok_host[i] = tokens[i];
-      }
-      VSIM_HIP(hipMemcpyAsync(m->tok_dev, m->tok_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-      if (m->arch == VSIM_ARCH_BLOOM) {  // word embeddings + word_embeddings_layernorm
-        RC(launch_get_rows(m->wte, E, V, m->tok_dev, N, m->cur1, s));
-        RC(launch_norm(m->cur1, m->inpL, E, N, m->emb_w, m->emb_b, s));
-        nk += 2;
-      } else {
-        RC(launch_get_rows(m->wte, E, V, m->tok_dev, N, m->inpL, s));
-        ++nk;
-      }
-    } else {
-      if (!resid_in) { set_error("eval: non-first stage needs resid_in"); return VSIM_EINVAL; }
-      VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
-    }
-    for (int il = m->l0; il < m->l1; ++il) RC(run_layer(m, il, n_past, N, nk));
+    RC(enqueue_prompt(m, n_past, tokens, N, resid_in, nk, "eval"));
     if (m->last) {
       // only the last row's logits leave the eval (vsim.cpp:736-737); rows are independent
       const float *xl = m->inpL + (size_t)(N - 1) * E;
@@ -2033,6 +2101,60 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   VSIM_HIP(hipStreamSynchronize(s));
   RC(spin_check(m));
   if (m->last && logits) memcpy(logits, m->logit_host, sizeof(float) * V);
+  m->kernels_last = nk;
+  if (m->profile) RC(prof_collect(m));
+  return VSIM_OK;
+}
+
+int vsim_score_set_chunk_rows(int rows) { return g_score_chunk_rows.exchange(rows > 0 ? rows : 0); }
+
+int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in,
+                          const int32_t *targets, double *logprob, int32_t *argmax, float *logits_all) {
+  if (!m) { set_error("eval_score: null model"); return VSIM_EINVAL; }
+  if (!m->last) { set_error("eval_score: needs the stage that owns the head (layer_end == n_layer)"); return VSIM_EINVAL; }
+  if (N <= 0 || n_past < 0 || n_past + N > m->n_ctx) { set_error("eval_score: n_past + N exceeds n_ctx"); return VSIM_EINVAL; }
+  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+  for (int i = 0; targets && i < N; ++i)
+    if (targets[i] < -1 || targets[i] >= V) { set_error("eval_score: target id outside [-1, n_vocab)"); return VSIM_EINVAL; }
+  m->st_npast = -1;  // as an eval: a stage step needs a new stage_begin
+  VSIM_HIP(hipSetDevice(m->device));
+  const ErrScope es(m);
+  RC(ensure_scratch(m, N));
+  const int C = score_chunk_rows(m);
+  RC(ensure_score_scratch(m, C));
+  hipStream_t s = m->stream;
+  int nk = 0;
+  RC(enqueue_prompt(m, n_past, tokens, N, resid_in, nk, "eval_score"));
+  for (int i = 0; i < N; ++i) m->score_tgt_host[i] = targets ? targets[i] : -1;
+  VSIM_HIP(hipMemcpyAsync(m->score_tgt, m->score_tgt_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  // the results of all rows: N doubles, then N ints (one copy out at the end)
+  double *lp_dev = (double *)m->score_out;
+  int32_t *am_dev = (int32_t *)(lp_dev + N);
+  // The head, C rows at a time: final LayerNorm, lm_head, k_score_rows.  mm() picks the product
+  // as for any prompt GEMM: exact mode the row-exact GEMV / GEMM (rows independent of the chunk);
+  // fast mode the fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else the
+  // quantize + GEMV path -- so fast-mode bits may depend on C.
+  for (int r0 = 0; r0 < N; r0 += C) {
+    const int c = std::min(C, N - r0);
+    const float *xl = m->inpL + (size_t)r0 * E;
+    const bool pf = m->mode == VSIM_MODE_FAST && c >= GEMM_MIN_N && m->pf_x16;
+    RC(pf ? launch_norm_f16q(xl, m->pf_x16, E, c, m->lnf_w, m->lnf_b, s)
+          : launch_norm(xl, m->cur1, E, c, m->lnf_w, m->lnf_b, s));
+    ++nk;
+    RC(mm(m, m->lmh, V, E, m->cur1, c, m->xq1, m->xd1, true, m->arch == VSIM_ARCH_GPTJ ? m->lmh_b : nullptr,
+          m->score_x, nk, pf ? m->pf_x16 : nullptr, nullptr, nullptr, nullptr, nullptr, "lm_head (score)"));
+    LAUNCH(m, nk, launch_score_rows(m->score_x, V, c, m->score_tgt + r0, lp_dev + r0, am_dev + r0, s), "k_score_rows",
+           (double)c * V * sizeof(float));
+    if (logits_all)
+      VSIM_HIP(hipMemcpyAsync(logits_all + (size_t)r0 * V, m->score_x, sizeof(float) * c * V, hipMemcpyDeviceToHost, s));
+  }
+  VSIM_HIP(hipMemcpyAsync(m->score_out_host, m->score_out, (size_t)N * (sizeof(double) + sizeof(int32_t)),
+                          hipMemcpyDeviceToHost, s));
+  RC(spin_read(m));
+  VSIM_HIP(hipStreamSynchronize(s));
+  RC(spin_check(m));
+  if (logprob) memcpy(logprob, m->score_out_host, sizeof(double) * N);
+  if (argmax) memcpy(argmax, (const double *)m->score_out_host + N, sizeof(int32_t) * N);
   m->kernels_last = nk;
   if (m->profile) RC(prof_collect(m));
   return VSIM_OK;

@@ -273,19 +273,11 @@ int norm_stats(unsigned *out2) {
 // ------------------------------------------------------------------ greedy argmax
 // Index of the largest logit with numpy.argmax's conventions: the first index among equal
 // maxima (-0.0 equal to +0.0), and the first NaN if there is one.  Each value and its index
-// become one 64-bit key whose unsigned order is that order: the value's bits mapped to an
-// unsigned order (NaN -> all ones, -0.0 -> +0.0) above ~index.  The workgroups reduce their
-// keys, fold them into ws[0] with one 64-bit atomic max each, then count themselves in ws[1];
-// the last to count reads the result and zeroes ws for the next launch.  r05: the single
+// become one 64-bit key whose unsigned order is that order (am_key, kern.hpp).  The workgroups
+// reduce their keys, fold them into ws[0] with one 64-bit atomic max each, then count themselves
+// in ws[1]; the last to count reads the result and zeroes ws for the next launch.  r05: the single
 // 1024-thread workgroup this replaced pulled the whole 50k-logit row through one CU, 14.45 us
 // per token (profiles/r05_exact_kernel_stats.csv).
-__device__ __forceinline__ unsigned long long am_key(float v, int i) {
-  uint32_t u = __float_as_uint(v);
-  if (v != v) u = 0xFFFFFFFFu;
-  else if (v == 0.0f) u = 0x80000000u;
-  else u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (0xFFFFFFFFu - (uint32_t)i);
-}
 constexpr int AM_T = 256, AM_MAX_WG = 64;
 static int am_grid(const float *x, int n) {
   const int n4 = ((uintptr_t)x & 15) ? 0 : n / 4;

@@ -48,6 +48,7 @@ EXPORTS = [
     "vsim_sampler_stats", "vsim_sampler_free", "vsim_model_eval_sample", "vsim_model_generate_sampled",
     "vsim_op_q4_quantize_w", "vsim_model_load_file_ex", "vsim_model_set_tensor_src", "vsim_quantize_set_chunk_rows",
     "vsim_quantize_file", "vsim_quantize_set_verbose",
+    "vsim_op_logprob", "vsim_model_eval_score", "vsim_score_set_chunk_rows",
 ]
 
 SRC_F32, SRC_F16 = 0, 1  # VSIM_SRC_*
@@ -244,6 +245,9 @@ def lib():
     L.vsim_quantize_set_chunk_rows.argtypes = [ci]
     L.vsim_quantize_file.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ci, ci, ctypes.POINTER(QuantizeStats)]
     L.vsim_quantize_set_verbose.argtypes = [ci]
+    L.vsim_op_logprob.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+    L.vsim_model_eval_score.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp]
+    L.vsim_score_set_chunk_rows.argtypes = [ci]
     _lib = L
     return L
 
@@ -347,6 +351,21 @@ def topk(x, n, win, scale, repeat_penalty, k, val, ids, stream=None):
                              addr(val), addr(ids), stream), "topk")
 
 
+def logprob(x, V, R, target, logprob, argmax, stream=None):
+    """vsim_op_logprob on device buffers (torch tensors or raw addresses): x float32 [R][V] (an int
+    address allows any 4-byte alignment), target int32 [R] or None (all -1), logprob float64 [R]
+    and argmax int32 [R] (either may be None).  Per row: log-softmax of the target's logit with the
+    sum in double and a fixed order, and the greedy id.  Enqueued on `stream`, not synchronized."""
+    def addr(t):
+        return t if isinstance(t, int) or t is None else ptr(t)
+    check(lib().vsim_op_logprob(addr(x), V, R, addr(target), addr(logprob), addr(argmax), stream), "logprob")
+
+
+def score_set_chunk_rows(rows: int) -> int:
+    """Rows per head chunk of Model.score (0 = default); returns the previous value."""
+    return int(lib().vsim_score_set_chunk_rows(int(rows)))
+
+
 def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,
               d=0, n_rot=0, style=0, clear=None, nclear=0, stream=None):
     """vsim_op_fast_gemv: jobs = [(w, rows, k, bias, y, epi, act)], operands torch tensors or None."""
@@ -440,6 +459,25 @@ class Model:
         lg = np.zeros(self.n_vocab, np.float32) if (want_logits and self.last) else None
         check(lib().vsim_model_eval(self.h, n_past, ptr(tok), N, ptr(resid_in), ptr(resid_out), ptr(lg)), "eval")
         return lg
+
+    def score(self, n_past, tokens=None, targets=None, resid_in=None, want_logits=False):
+        """vsim_model_eval_score: the prompt pass over `tokens` (or a last stage's resid_in) at
+        n_past, then per position the log-probability of targets[i] and the greedy id, computed on
+        the device.  targets=None scores each token's successor: tokens[1:] + [-1] (-1: nothing
+        to score).  Returns (logprob float64 [N], argmax int32 [N]) and, with want_logits, every
+        logits row [N][n_vocab] too."""
+        N = len(tokens) if tokens is not None else int(resid_in.shape[0])
+        tok = np.ascontiguousarray(tokens, np.int32) if tokens is not None else None
+        if targets is None:
+            targets = list(tokens[1:]) + [-1] if tokens is not None else [-1] * N
+        tgt = np.ascontiguousarray(targets, np.int32)
+        if tgt.size != N:
+            raise ValueError("score: one target per position")
+        lp, am = np.zeros(N, np.float64), np.zeros(N, np.int32)
+        lg = np.zeros((N, self.n_vocab), np.float32) if want_logits else None
+        check(lib().vsim_model_eval_score(self.h, n_past, ptr(tok), N, ptr(resid_in), ptr(tgt), ptr(lp), ptr(am),
+                                          ptr(lg)), "score")
+        return (lp, am, lg) if want_logits else (lp, am)
 
     def eval_argmax(self, n_past, token) -> int:
         """Greedy decode step: the next token (argmax of the logits, taken on the device)."""

@@ -8,7 +8,8 @@
 // this file is host control only: the sampler too is the library's (vsim_sampler_*).
 // Extra flags: --device N, --mode exact|fast, --n_ctx N (reference: fixed 512,
 // vsim.cpp:758), --no-graph, --sampler host|device, --quantize (load an F32 / F16 file as the
-// converters write it, quantized to Q4_0 on the device while it loads).
+// converters write it, quantized to Q4_0 on the device while it loads), --score (the -p ids are a
+// text to score: per-position log-probabilities and the perplexity, vsim_model_eval_score).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -42,6 +43,8 @@ struct Params {
   bool graph = true;
   bool device_sampler = true;
   bool quantize = false;
+  bool score = false;
+  bool batch_given = false;  // -b on the command line (--score: the window stride)
 };
 
 void usage(const char *argv0, const Params &p) {
@@ -61,6 +64,9 @@ void usage(const char *argv0, const Params &p) {
   fprintf(stderr, "  --n_ctx N             context length (default 512, as the reference)\n");
   fprintf(stderr, "  --no-graph            launch every kernel eagerly\n");
   fprintf(stderr, "  --quantize            the model file is F32 / F16: quantize it to Q4_0 on the GPU while loading\n");
+  fprintf(stderr, "  --score               score the -p ids as a text instead of generating: one line per position\n");
+  fprintf(stderr, "                        (pos id logprob argmax), then nll / perplexity / top-1; windows of n_ctx\n");
+  fprintf(stderr, "                        tokens, -b = the window stride (default: the window)\n");
   fprintf(stderr, "  --sampler host|device device = penalty, temperature and top-k on the GPU (default);\n");
   fprintf(stderr, "                        host = the logits row is copied out and sampled on the CPU\n");
 }
@@ -85,7 +91,7 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "--temp") p.temp = std::stof(next());
     else if (a == "--repeat_last_n") p.repeat_last_n = std::stoi(next());
     else if (a == "--repeat_penalty") p.repeat_penalty = std::stof(next());
-    else if (a == "-b" || a == "--batch_size") p.n_batch = std::stoi(next());
+    else if (a == "-b" || a == "--batch_size") { p.n_batch = std::stoi(next()); p.batch_given = true; }
     else if (a == "-m" || a == "--model") p.model = next();
     else if (a == "--return_logits") p.return_logits = true;
     else if (a == "--device") p.device = std::stoi(next());
@@ -93,6 +99,7 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "--n_ctx") p.n_ctx = std::stoi(next());
     else if (a == "--no-graph") p.graph = false;
     else if (a == "--quantize") p.quantize = true;
+    else if (a == "--score") p.score = true;
     else if (a == "--sampler") {
       const std::string v = next();
       if (v != "host" && v != "device") {
@@ -158,6 +165,43 @@ void print_kernel_table(vsim_model *model) {
   printf("%-54s: %10.3f %6.1f%%\n", "COMPUTE (sum)", tot, 100.0);
 }
 
+// --score: the text in windows of n_ctx tokens, each evaluated from n_past = 0.  The first window
+// scores all its positions; each later one moves `stride` positions on, keeps the n_ctx - stride
+// tokens before them as context (targets -1) and scores only the new ones (vsim_amd/score.py's
+// perplexity).  Position p scores ids[p + 1]; a line is "pos id logprob argmax" for pos = p + 1.
+int run_score(vsim_model *model, const std::vector<int32_t> &ids, int window, int stride) {
+  const int n = (int)ids.size();
+  if (stride < 1 || stride > window) stride = window;
+  double sum = 0.0;
+  long scored = 0, hits = 0;
+  std::vector<int32_t> tgt, am;
+  std::vector<double> lp;
+  for (int done = 0, first_window = 1; done < n - 1; first_window = 0) {
+    const int end = std::min(n, first_window ? window : done + stride), start = std::max(0, end - window);
+    const int N = end - start;
+    tgt.assign(N, -1);
+    lp.assign(N, 0.0);
+    am.assign(N, 0);
+    for (int p = std::max(start, done); p < end && p < n - 1; ++p) tgt[p - start] = ids[p + 1];
+    if (vsim_model_eval_score(model, 0, ids.data() + start, N, nullptr, tgt.data(), lp.data(), am.data(), nullptr) !=
+        VSIM_OK) {
+      fprintf(stderr, "score failed: %s\n", vsim_last_error());
+      return 1;
+    }
+    for (int p = done; p < end && p < n - 1; ++p) {
+      printf("%d %d %.17g %d\n", p + 1, ids[p + 1], lp[p - start], am[p - start]);
+      sum += lp[p - start];
+      hits += am[p - start] == ids[p + 1];
+      ++scored;
+    }
+    done = end;
+  }
+  const double nll = scored ? -sum / (double)scored : NAN;
+  printf("score: tokens=%ld nll=%.17g ppl=%.17g top1=%.6f\n", scored, nll, std::exp(nll),
+         scored ? (double)hits / (double)scored : NAN);
+  return 0;
+}
+
 int run(const Params &params, int arch) {
   const double t_start = now_s();
   const vsim_sample_params sp = {params.seed,  params.top_k, params.repeat_last_n,
@@ -193,6 +237,13 @@ int run(const Params &params, int arch) {
   const double t_load = now_s() - t_start;
 
   std::vector<int32_t> embd_inp = whitespace_tokenize(params.prompt);
+  if (params.score) {
+    const int rc = run_score(model, embd_inp, n_ctx, params.batch_given ? params.n_batch : n_ctx);
+    fflush(stdout);
+    vsim_sampler_free(sampler);
+    vsim_model_free(model);
+    return rc;
+  }
   int n_predict = std::min(params.n_predict, n_ctx - (int)embd_inp.size());
   printf("\n%s: prompt: '%s'\n%s: number of tokens in prompt = %zu\n\n", __func__, params.prompt.c_str(), __func__,
          embd_inp.size());
