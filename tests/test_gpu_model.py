@@ -232,6 +232,52 @@ def test_kernel_counts_per_graph_kind(tmp_path):
     m.close()
 
 
+# kernels_per_eval of eval(0, ids) for N = 5 (below GEMM_MIN_N), 72 (an fp16 batch without the
+# 256-wide GEMM) and 288 (>= G2_MIN_N: the RoPE, pair, KV-fp16 and join epilogues).  Each is the
+# sum of the launch list:
+#   embedding 1 (BLOOM 2: + its LayerNorm), the head 3 (norm, quantize, GEMV), and per layer
+#   exact / N = 5: norm, Q (quantize + GEMV), K, V, KV write, KQ, softmax, KQV, out-proj (2), [MLP
+#     norm, quantize: not GPT-J], fc_in, GELU, fc_out (2), join = 16 (GPT-J) / 18 (GPT-NeoX) / 19
+#     (serial GPT-NeoX, BLOOM: + the x + attn add)
+#   fast, N = 72: no quantize launches, one fp16 operand pass after the attention (not at head dim
+#     256) and one with the GELU, the attention 2 launches (BLOOM: 3) = 13 / 12 / 14 / 15 / 16 for
+#     GPT-J / GPT-J at head dim 256 / GPT-NeoX / serial GPT-NeoX / BLOOM
+#   fast, N = 288: GELU-quantize in fc_in's epilogue and the join in fc_out's (not BLOOM); GPT-J:
+#     RoPE + KV write in Q/K/V's, Q and K one launch = 9 / 8 / 12 / 13 / 15
+PROMPT_KERNELS = {
+    "small-gptj": {"exact": (36, 36, 36), "fast": (36, 30, 22)},
+    "small-neox": {"exact": (40, 40, 40), "fast": (40, 32, 28)},
+    "small-neox-serial": {"exact": (42, 42, 42), "fast": (42, 34, 30)},
+    "small-bloom": {"exact": (43, 43, 43), "fast": (43, 37, 35)},
+    "gptj-d256": {"exact": (36, 36, 36), "fast": (36, 28, 20)},
+}
+
+
+@pytest.mark.parametrize("mode", ["exact", "fast"])
+@pytest.mark.parametrize("cfg", sorted(PROMPT_KERNELS))
+def test_prompt_kernel_counts(cfg, mode):
+    """The prompt path's launch count per graph, mode and batch size.  It is summed by hand
+    (++nk beside every launch), so it is what one layer function for all graphs gets wrong first
+    without changing a logit.  gptj-d256: head dim 256, the only width at which the attention
+    writes the out-projection's fp16 operand itself."""
+    if cfg == "gptj-d256":
+        arch_s, hp = "gptj", mg.HParams(512, 512, 2, 2, 64)
+    else:
+        arch_s, hp = mg.CONFIGS[cfg.replace("-serial", "")]
+    arch = {"gptj": hip.ARCH_GPTJ, "gptneox": hip.ARCH_GPTNEOX, "bloom": hip.ARCH_BLOOM}[arch_s]
+    par = 0 if cfg.endswith("-serial") else hp.use_parallel_residual
+    m = hip.Model.create(arch, dict(n_vocab=hp.n_vocab, n_embd=hp.n_embd, n_head=hp.n_head, n_layer=hp.n_layer,
+                                    n_rot=hp.n_rot, use_parallel_residual=par))
+    m.randomize(11, 0.05)
+    m.set_mode(hip.MODE_FAST if mode == "fast" else hip.MODE_EXACT)
+    got = []
+    for N in (5, 72, 288):
+        m.eval(0, [(7 * i + 3) % hp.n_vocab for i in range(N)])
+        got.append(m.info()["kernels_per_eval"])
+    m.close()
+    assert tuple(got) == PROMPT_KERNELS[cfg][mode]
+
+
 @pytest.mark.parametrize("cfg", ["tiny-neox", "tiny-gptj"])
 def test_scratch_regrow_under_captured_graphs(cfg, tmp_path):
     """A prompt longer than the scratch (sized for 16 tokens) frees and regrows every scratch

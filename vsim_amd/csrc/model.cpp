@@ -7,8 +7,10 @@
 // host sends the token ids and receives one logits row (vsim.cpp:736-737).
 // A pipeline stage owns layers [l0, l1); stages exchange the residual inpL ([N][E] f32).
 //
-// What the host side keeps is described once each: the tensors of an architecture
-// (arch_table: plan_slots and bind_pointers walk it), the scratch buffers (scratch_table:
+// What the host side keeps is described once each: what distinguishes the three graphs
+// (GraphDesc: the one prompt layer, run_layer, the head and the decode steps branch on it), the
+// operands of a prompt product (Product: PromptBatch::mm picks the kernel), the tensors of an
+// architecture (arch_table: plan_slots and bind_pointers walk it), the scratch buffers (scratch_table:
 // allocated, freed and poisoned from it), the five single-token step graphs (StepGraph
 // step[5], captured by decode_graph) and what a step of each kind enqueues (enqueue_step:
 // the captured and the eager form are the same call).  LAUNCH brackets a profiled launch.
@@ -69,10 +71,29 @@ struct StepGraph {
   int kernels = 0;  // kernels in one replay
 };
 
+// What distinguishes the three graphs, filled once from arch and use_parallel_residual
+// (model_create_impl); the prompt layer, the head and the decode steps branch on these alone.
+enum Rotary { ROT_NONE, ROT_NEOX, ROT_GPTJ };  // none (BLOOM), rotate-half, interleaved pairs
+// The MLP's input and the layer's output: parallel (x + attn + ff, the MLP beside the attention);
+// serial adding to the old row (GPT-NeoX with use_parallel_residual = 0: the MLP reads
+// LN(x + attn), the layer ends x + attn + ff all the same, vsim.cpp:626-658); serial keeping the
+// joined row (BLOOM: inpFF = x + attn is the residual, the layer ends inpFF + ff)
+enum Residual { RES_PARALLEL, RES_SERIAL_OLD, RES_SERIAL_JOINED };
+struct GraphDesc {
+  Rotary rotary = ROT_NEOX;
+  bool qkvo_bias = true;   // Q, K, V and the out-projection carry biases
+  bool alibi = false;      // the softmax adds the head slopes' bias
+  bool two_norms = true;   // a LayerNorm of its own for the MLP (false: the input norm feeds both)
+  Residual residual = RES_PARALLEL;
+  bool emb_norm = false;   // LayerNorm on the embedding rows
+  bool lmh_bias = false;   // bias on the lm_head
+};
+
 }  // namespace
 
 struct vsim_model {
   int arch = VSIM_ARCH_GPTNEOX;
+  GraphDesc gd;
   unsigned *err_dev = nullptr, *err_host = nullptr;  // this model's bounded-wait timeouts (spin_check)
   unsigned err_seen = 0;
   vsim_hparams hp{};
@@ -503,6 +524,15 @@ bool is_fused_qkv(const vsim_model *m, const std::string &n) {
     if (rc_) return rc_;         \
   } while (0)
 
+// part(slot name, byte offset, bytes) for each of a fused tensor's row blocks: the caller's
+// nbytes in thirds.  `who` prefixes the error message.
+template <class Fn>
+int for_qkv_parts(const std::string &n, size_t nbytes, const char *who, Fn part) {
+  if (nbytes % 3 != 0) { set_error(std::string(who) + ": fused qkv size"); return VSIM_EINVAL; }
+  for (int i = 0; i < 3; ++i) RC(part((n + QKV_PARTS[i]).c_str(), i * (nbytes / 3), nbytes / 3));
+  return VSIM_OK;
+}
+
 // Bounded cross-workgroup waits that gave up (k_layer_tail, the barrier-free chain GEMV, the
 // stream-K finisher) count into the model's own device word (m->err_dev: every launch this model
 // enqueues gets it through ErrScope, so another model's or a standalone op's timeout never fails
@@ -587,124 +617,100 @@ int prof_collect(vsim_model *m) {
 
 double w4_algo_bytes(const W4 &w) { return (double)w.rows * w.k / QK * QBYTES; }
 
-// Quantize an activation and run one GEMV in the model's mode.  x16 non-null (fast-mode
-// prompt batches): the activation is already the GEMM's fp16 operand (launch_act_quant_f16).
-// gq (fc_in of a long prompt): bias gq_bias + GELU + quantize of the product straight into the
-// next GEMM's fp16 operand gq, in the GEMM's epilogue; epi: RoPE or the residual join in the
-// epilogue (G2Epi); *fused tells the caller whether either ran.  what: the profile's name for the
-// product instead of the kernel's.
-int mm(vsim_model *m, const void *W, int M, int K, const float *x, int N, uint8_t *xq, float *xd, bool quantize,
-       const float *bias, float *y, int &nk, const void *x16 = nullptr, void *gq = nullptr,
-       const float *gq_bias = nullptr, bool *fused = nullptr, const G2Epi *epi = nullptr,
-       const char *what = nullptr) {
-  if (fused) *fused = false;
-  if (quantize && !x16) {
-    RC(launch_q4_quantize(x, K, N, xq, xd, m->stream));
+// One product of a Q4_0 weight with the batch's activation rows (PromptBatch::mm).  Every operand
+// defaults to absent; a call site names what it sets (designated initializers, in this order).
+struct Product {
+  W4 w{};                     // the weight, [M = w.rows][K = w.k]
+  const float *x = nullptr;   // the rows as f32 ...
+  uint8_t *xq = nullptr;      // ... and as Q4 activations with their factors xd:
+  float *xd = nullptr;
+  bool quantize = false;      // made from x by this call, or left there by an earlier one
+  const float *bias = nullptr;
+  float *y = nullptr;
+  // fast-mode prompt batches: the rows are already the GEMM's fp16 operand (launch_act_quant_f16,
+  // launch_norm_f16q), and x / xq / xd go unused
+  const void *x16 = nullptr;
+  // fc_in of a long prompt: bias gq_bias + GELU + quantize of the product straight into the next
+  // GEMM's fp16 operand gq, in the GEMM's epilogue
+  void *gq = nullptr;
+  const float *gq_bias = nullptr;
+  const G2Epi *epi = nullptr;  // RoPE or the residual join in the long prompt GEMM's epilogue
+  const char *what = nullptr;  // the profile's name for the product instead of the kernel's
+  bool fused = false;          // out: the GELU-quantize or the G2Epi epilogue ran
+};
+
+// One prompt batch on its way through the layers and the head: N rows at n_past, counting its
+// launches into nk.
+struct PromptBatch {
+  vsim_model *m;
+  int N, n_past;
+  int &nk;
+  // fast-mode batch: every activation goes once from f32 to the GEMM's fp16 operand
+  // (quantize_row_q4_0 values, k_act_quant_f16; the GELU folded into fc_out's), in the model's
+  // scratch pf_x16: xa [N][E] norm outputs, then xb [N][F] attention / GELU outputs
+  bool pf;
+  void *xa, *xb;
+  PromptBatch(vsim_model *m_, int N_, int n_past_, int &nk_)
+      : m(m_), N(N_), n_past(n_past_), nk(nk_), pf(m_->mode == VSIM_MODE_FAST && N_ >= GEMM_MIN_N && m_->pf_x16),
+        xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N_ * E_(m_)) : nullptr) {}
+
+  int act16(const float *x, int K, void *x16, const float *gbias, bool gelu) {
+    if (!pf) return VSIM_OK;
     ++nk;
+    return launch_act_quant_f16(x, K, N, gbias, gelu, x16, m->stream);
   }
-  // long prompt: the 256-wide-tile GEMM, the Q4_0 weight dequantized to fp16 in LDS
-  if (x16 && N >= G2_MIN_N && K % 64 == 0) {
-    const bool gelu = gq && gq_bias && M % QK == 0;
+  // LayerNorm + affine (vsim.cpp:526-533); fast-mode batch: straight to the GEMM's fp16 operand
+  int norm(const float *x, float *y, const float *w, const float *b, void *x16) {
+    ++nk;
+    return pf ? launch_norm_f16q(x, x16, E_(m), N, w, b, m->stream) : launch_norm(x, y, E_(m), N, w, b, m->stream);
+  }
+  // Quantize the activation (unless it is an fp16 operand already) and run the product in the
+  // model's mode.
+  int mm(Product &P) {
+    const int M = P.w.rows, K = P.w.k;
+    P.fused = false;
+    if (P.quantize && !P.x16) {
+      RC(launch_q4_quantize(P.x, K, N, P.xq, P.xd, m->stream));
+      ++nk;
+    }
+    // long prompt: the 256-wide-tile GEMM, the Q4_0 weight dequantized to fp16 in LDS
+    if (P.x16 && N >= G2_MIN_N && K % 64 == 0) {
+      const bool gelu = P.gq && P.gq_bias && M % QK == 0;
+      LAUNCH(m, nk,
+             launch_gemm_q4_256(P.w, P.x16, N, gelu ? P.gq_bias : P.bias, P.y, m->stream, gelu ? P.gq : nullptr,
+                                gelu ? nullptr : P.epi),
+             P.what ? P.what : "k_gemm_f16_256 (prompt)", w4_algo_bytes(P.w));
+      P.fused = gelu || P.epi;
+      return VSIM_OK;
+    }
     LAUNCH(m, nk,
-           launch_gemm_q4_256(w4_view(W, M, K), x16, N, gelu ? gq_bias : bias, y, m->stream, gelu ? gq : nullptr,
-                              gelu ? nullptr : epi),
-           what ? what : "k_gemm_f16_256 (prompt)", (double)M * K / QK * QBYTES);
-    if (fused) *fused = gelu || epi;
+           P.x16 ? launch_gemm_f16x(P.w, P.x16, N, P.bias, P.y, m->stream)
+                 : launch_q4_gemv(P.w.qs, M, K, P.xq, P.xd, N, P.bias, P.y, m->mode, m->stream),
+           P.what ? P.what : P.x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
+           w4_algo_bytes(P.w));
     return VSIM_OK;
   }
-  LAUNCH(m, nk,
-         x16 ? launch_gemm_f16x(w4_view(W, M, K), x16, N, bias, y, m->stream)
-             : launch_q4_gemv(W, M, K, xq, xd, N, bias, y, m->mode, m->stream),
-         what ? what : x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
-         (double)M * K / QK * QBYTES);
-  return VSIM_OK;
-}
+};
 
-// The BLOOM layer (oracle eval_bloom): LN -> q/k/v (+bias) -> KV write -> KQ -> scale ->
-// alibi -> mask -> softmax -> KQV -> wo (+bias) -> inpFF = attn + inpL -> LN -> w1 (+bias) ->
-// GELU -> w2 (+bias) -> inpL = ff + inpFF.
-int run_layer_bloom(vsim_model *m, int il, int n_past, int N, int &nk) {
+// One layer of a prompt batch, for all three graphs: LN -> Q/K/V (+bias) -> KV write (+ RoPE) ->
+// KQ -> scale (-> ALiBi) -> mask -> softmax -> KQV -> out-projection (+bias) -> the MLP's input ->
+// fc_in (+bias) -> GELU -> fc_out (+bias) -> residual join (GPT-NeoX: vsim.cpp:526-695; BLOOM:
+// oracle eval_bloom, inpFF = attn + inpL -> LN -> w1 -> GELU -> w2 -> inpL = ff + inpFF).  What
+// differs between them is GraphDesc's.
+int run_layer(PromptBatch &B, int il) {
+  vsim_model *m = B.m;
+  const GraphDesc &G = m->gd;
   const LayerW &L = m->layers[il - m->l0];
-  const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
+  const int N = B.N, n_past = B.n_past, E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
+  int &nk = B.nk;
   hipStream_t s = m->stream;
-  // fast-mode prompt batch: GEMM operands straight to fp16 in the model's scratch (as run_layer)
-  const bool pf = m->mode == VSIM_MODE_FAST && N >= GEMM_MIN_N && m->pf_x16;
-  void *xa = pf ? m->pf_x16 : nullptr;
-  void *xb = pf ? (void *)((uint16_t *)m->pf_x16 + (size_t)N * E) : nullptr;
-  auto act16 = [&](const float *x, int K, void *x16, const float *gbias, bool gelu) -> int {
-    if (!pf) return VSIM_OK;
-    ++nk;
-    return launch_act_quant_f16(x, K, N, gbias, gelu, x16, s);
-  };
-  // LayerNorm (straight to the GEMM's fp16 operand in a prompt batch)
-  auto norm = [&](const float *x, float *y, const float *w, const float *b, void *x16) -> int {
-    ++nk;
-    return pf ? launch_norm_f16q(x, x16, E, N, w, b, s) : launch_norm(x, y, E, N, w, b, s);
-  };
-  RC(norm(m->inpL, m->cur1, L.ln1_w, L.ln1_b, xa));
-  RC(mm(m, L.wq, E, E, m->cur1, N, m->xq1, m->xd1, true, L.bq, m->Qb, nk, xa));
-  RC(mm(m, L.wk, E, E, m->cur1, N, m->xq1, m->xd1, false, L.bk, m->Kb, nk, xa));
-  RC(mm(m, L.wv, E, E, m->cur1, N, m->xq1, m->xd1, false, L.bv, m->Vb, nk, xa));
-  const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
-  float *kc = m->kcache + loff, *vc = m->vcache + loff;
-  RC(launch_rope_kv_write(0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past, 0, m->rope_cs, s)); ++nk;  // no rotary
-  const int nkv = n_past + N;
-  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
-  RC(launch_kq(kc, E, m->Qb, E, d, H, nkv, N, m->kq, s, n_past)); ++nk;
-  RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s, m->alibi)); ++nk;
-  RC(launch_kqv(vc, E, m->kq, d, H, nkv, N, m->attn_in, 1, s, n_past)); ++nk;
-  RC(act16(m->attn_in, E, xb, nullptr, false));
-  RC(mm(m, L.wo, E, E, m->attn_in, N, m->xq2, m->xd2, true, L.bo, m->attn, nk, xb));
-  // inpFF = attn + inpL (kept in cur2), its LayerNorm into cur1
-  VSIM_HIP(hipMemcpyAsync(m->cur2, m->attn, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
-  RC(launch_add_bias(m->cur2, m->inpL, N * E, 1, s)); ++nk;
-  RC(norm(m->cur2, m->cur1, L.ln2_w, L.ln2_b, xa));
-  bool gq = false;
-  RC(mm(m, L.wfc, F, E, m->cur1, N, m->xq2, m->xd2, true, nullptr, m->fch, nk, xa, xb, L.bfc, &gq));
-  if (pf) {
-    if (!gq) RC(act16(m->fch, F, xb, L.bfc, true));  // bias + GELU + quantize, one pass
-  } else {
-    RC(launch_gelu(m->fch, m->fch, N * F, L.bfc, F, s)); ++nk;
-  }
-  RC(mm(m, L.wproj, E, F, m->fch, N, m->xq3, m->xd3, true, L.bproj, m->ff, nk, xb));
-  // inpL = ff + inpFF
-  VSIM_HIP(hipMemcpyAsync(m->inpL, m->cur2, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
-  RC(launch_add_bias(m->inpL, m->ff, N * E, 1, s)); ++nk;
-  return VSIM_OK;
-}
-
-int run_layer(vsim_model *m, int il, int n_past, int N, int &nk) {
-  if (m->arch == VSIM_ARCH_BLOOM) return run_layer_bloom(m, il, n_past, N, nk);
-  const LayerW &L = m->layers[il - m->l0];
-  const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
-  const bool gptj = m->arch == VSIM_ARCH_GPTJ;
-  hipStream_t s = m->stream;
-  // fast-mode prompt batch: every activation goes once from f32 to the GEMM's fp16 operand
-  // (quantize_row_q4_0 values, k_act_quant_f16; the GELU folded into fc_out's)
-  // (operands in the model's scratch, pf_x16: [N][E] norm outputs, then [N][F] attention /
-  // GELU outputs)
-  const bool pf = m->mode == VSIM_MODE_FAST && N >= GEMM_MIN_N && m->pf_x16;
-  struct {
-    void *a, *b;
-  } X = {m->pf_x16, pf ? (void *)((uint16_t *)m->pf_x16 + (size_t)N * E) : nullptr};
-  if (!pf) X.a = nullptr;
-  auto act16 = [&](const float *x, int K, void *x16, const float *gbias, bool gelu) -> int {
-    if (!pf) return VSIM_OK;
-    ++nk;
-    return launch_act_quant_f16(x, K, N, gbias, gelu, x16, s);
-  };
-  // input LayerNorm + affine (vsim.cpp:526-533)
-  auto norm = [&](const float *x, float *y, const float *w, const float *b, void *x16) -> int {
-    ++nk;  // (prompt batch: straight to the GEMM's fp16 operand)
-    return pf ? launch_norm_f16q(x, x16, E, N, w, b, s) : launch_norm(x, y, E, N, w, b, s);
-  };
-  RC(norm(m->inpL, m->cur1, L.ln1_w, L.ln1_b, X.a));
+  RC(B.norm(m->inpL, m->cur1, L.ln1_w, L.ln1_b, B.xa));
   const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
   float *kc = m->kcache + loff, *vc = m->vcache + loff;
   // long GPT-J prompt: RoPE and the KV-cache write (vsim.cpp:553-580) in the Q/K/V GEMMs'
   // epilogues -- K and V straight into their cache rows -- instead of a pass of their own
-  const bool g2 = pf && N >= G2_MIN_N && E % 64 == 0;
-  const bool rope_epi = g2 && gptj;
+  const bool g2 = B.pf && N >= G2_MIN_N && E % 64 == 0;
+  const bool rope_epi = g2 && G.rotary == ROT_GPTJ;
   G2Epi er;
   er.cs = m->rope_cs;
   er.d = d;
@@ -712,8 +718,9 @@ int run_layer(vsim_model *m, int il, int n_past, int N, int &nk) {
   er.p0 = n_past;
   float *kout = rope_epi ? kc + (size_t)n_past * E : m->Kb, *vout = rope_epi ? vc + (size_t)n_past * E : m->Vb;
   // ... and the new keys' fp16 copies for the prompt attention (K rows, V^T columns), which
-  // then converts only the cached keys before them
-  const bool attn16 = m->mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
+  // then converts only the cached keys before them.  (ALiBi lives in the softmax kernel only:
+  // BLOOM keeps the KQ / softmax / KQV kernels in both modes.)
+  const bool attn16 = !G.alibi && m->mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
   if (attn16) RC(ensure_pf_scratch(m));
   const bool kv16_epi = rope_epi && attn16;
   G2Epi ek = er, ev;
@@ -724,82 +731,89 @@ int run_layer(vsim_model *m, int il, int n_past, int N, int &nk) {
     ev.h16_ld = attn_prefill_ldt(n_past + N);
     ev.p0 = n_past;
   }
-  // Q, K, V (+ bias for GPT-NeoX, vsim.cpp:540-547); a long GPT-J prompt's Q and K (both RoPE
-  // epilogues, no bias) as one launch of both tile grids
+  // Q, K, V (+ bias, vsim.cpp:540-547) on the input norm's rows, which Q's call quantizes for all
+  // three; a long GPT-J prompt's Q and K (both RoPE epilogues, no bias) as one launch of both
+  // tile grids
+  Product q{.w = w4_view(L.wq, E, E), .x = m->cur1, .xq = m->xq1, .xd = m->xd1, .quantize = true,
+            .bias = G.qkvo_bias ? L.bq : nullptr, .y = m->Qb, .x16 = B.xa, .epi = rope_epi ? &er : nullptr};
+  Product k{.w = w4_view(L.wk, E, E), .xq = m->xq1, .xd = m->xd1, .bias = G.qkvo_bias ? L.bk : nullptr, .y = kout,
+            .x16 = B.xa, .epi = rope_epi ? &ek : nullptr};
+  Product v{.w = w4_view(L.wv, E, E), .xq = m->xq1, .xd = m->xd1, .bias = G.qkvo_bias ? L.bv : nullptr, .y = vout,
+            .x16 = B.xa, .epi = kv16_epi ? &ev : nullptr};
   if (rope_epi && gemm_pair_enabled(E, E)) {
-    LAUNCH(m, nk, launch_gemm_q4_256_pair(w4_view(L.wq, E, E), w4_view(L.wk, E, E), X.a, N, m->Qb, kout, er, ek, s),
-           "k_gemm_f16_256 (prompt)", 2.0 * E * E / QK * QBYTES);
+    LAUNCH(m, nk, launch_gemm_q4_256_pair(q.w, k.w, B.xa, N, m->Qb, kout, er, ek, s), "k_gemm_f16_256 (prompt)",
+           2.0 * E * E / QK * QBYTES);
   } else {
-    RC(mm(m, L.wq, E, E, m->cur1, N, m->xq1, m->xd1, true, gptj ? nullptr : L.bq, m->Qb, nk, X.a, nullptr, nullptr,
-          nullptr, rope_epi ? &er : nullptr));
-    RC(mm(m, L.wk, E, E, m->cur1, N, m->xq1, m->xd1, false, gptj ? nullptr : L.bk, kout, nk, X.a, nullptr, nullptr,
-          nullptr, rope_epi ? &ek : nullptr));
+    RC(B.mm(q));
+    RC(B.mm(k));
   }
-  RC(mm(m, L.wv, E, E, m->cur1, N, m->xq1, m->xd1, false, gptj ? nullptr : L.bv, vout, nk, X.a, nullptr, nullptr,
-        nullptr, kv16_epi ? &ev : nullptr));
-  // KV write + RoPE (vsim.cpp:553-580)
+  RC(B.mm(v));
+  // KV write + RoPE (vsim.cpp:553-580; BLOOM: the write alone)
   if (!rope_epi) {
-    RC(launch_rope_kv_write(gptj ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past, m->hp.n_rot, m->rope_cs, s));
+    RC(launch_rope_kv_write(G.rotary == ROT_GPTJ ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past,
+                            G.rotary == ROT_NONE ? 0 : m->hp.n_rot, m->rope_cs, s));
     ++nk;
   }
   // attention (vsim.cpp:583-616)
   const int nkv = n_past + N;
   const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
   // (head dim 256: the attention writes the out-projection's fp16 operand itself)
-  const bool attn_q16 = attn16 && pf && attn_prefill_quantizes(d);
+  const bool attn_q16 = attn16 && B.pf && attn_prefill_quantizes(d);
   if (attn16) {
     // fast-mode prompt: one-pass fp16 MFMA attention (attn_prefill.hip)
     RC(launch_attn_prefill_f16(m->Qb, kc, vc, d, H, N, n_past, scale, m->attn_in, s, m->pf_scratch, m->pf_bytes,
-                               kv16_epi, attn_q16 ? X.b : nullptr));
+                               kv16_epi, attn_q16 ? B.xb : nullptr));
     nk += 2;
   } else {
     RC(launch_kq(kc, E, m->Qb, E, d, H, nkv, N, m->kq, s, n_past)); ++nk;
-    RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s)); ++nk;
+    RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s, G.alibi ? m->alibi : nullptr)); ++nk;
     RC(launch_kqv(vc, E, m->kq, d, H, nkv, N, m->attn_in, 1, s, n_past)); ++nk;
   }
-  if (!attn_q16) RC(act16(m->attn_in, E, X.b, nullptr, false));
-  RC(mm(m, L.wo, E, E, m->attn_in, N, m->xq2, m->xd2, true, gptj ? nullptr : L.bo, m->attn, nk, X.b));
-  // feed-forward input
-  const uint8_t *fxq = m->xq1;
-  const float *fxd = m->xd1;
-  bool fquant = false;
-  const float *fx = m->cur1;
-  if (!gptj) {
-    if (m->hp.use_parallel_residual) {
-      RC(norm(m->inpL, m->cur2, L.ln2_w, L.ln2_b, X.a));
-    } else {
-      // inpFF = cur + inpL ; norm ; affine  (vsim.cpp:631-649)
+  if (!attn_q16) RC(B.act16(m->attn_in, E, B.xb, nullptr, false));
+  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = true,
+            .bias = G.qkvo_bias ? L.bo : nullptr, .y = m->attn, .x16 = B.xb};
+  RC(B.mm(o));
+  // fc_in (its bias goes with the GELU) reads the input norm's quantized row again, or the MLP's
+  // own norm: of x (parallel), or of x + attn, joined in cur2 (vsim.cpp:631-649) and normalized in
+  // place -- unless the joined row is the residual and stays there (BLOOM: the norm goes to cur1)
+  const bool serial = G.residual != RES_PARALLEL, keep_joined = G.residual == RES_SERIAL_JOINED;
+  Product fi{.w = w4_view(L.wfc, F, E), .xq = m->xq1, .xd = m->xd1, .y = m->fch, .x16 = B.xa, .gq = B.xb,
+             .gq_bias = L.bfc};
+  if (G.two_norms) {
+    if (serial) {
       VSIM_HIP(hipMemcpyAsync(m->cur2, m->attn, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
       RC(launch_add_bias(m->cur2, m->inpL, N * E, 1, s)); ++nk;  // cur + inpL elementwise
-      RC(norm(m->cur2, m->cur2, L.ln2_w, L.ln2_b, X.a));
     }
-    fx = m->cur2;
-    fxq = m->xq2;
-    fxd = m->xd2;
-    fquant = true;
+    float *ny = keep_joined ? m->cur1 : m->cur2;
+    RC(B.norm(serial ? m->cur2 : m->inpL, ny, L.ln2_w, L.ln2_b, B.xa));
+    fi.x = ny;
+    fi.xq = m->xq2;
+    fi.xd = m->xd2;
+    fi.quantize = true;
   }
-  // (the norms above wrote the prompt batch's fp16 operand already)
-  bool gq = false;
-  RC(mm(m, L.wfc, F, E, fx, N, (uint8_t *)fxq, (float *)fxd, fquant, nullptr, m->fch, nk, X.a, X.b, L.bfc, &gq));
-  if (pf) {
-    if (!gq) RC(act16(m->fch, F, X.b, L.bfc, true));  // bias + GELU + quantize, one pass
+  RC(B.mm(fi));
+  if (B.pf) {
+    if (!fi.fused) RC(B.act16(m->fch, F, B.xb, L.bfc, true));  // bias + GELU + quantize, one pass
   } else {
     RC(launch_gelu(m->fch, m->fch, N * F, L.bfc, F, s)); ++nk;
   }
-  // fc_out; a long prompt joins the residual in its epilogue (vsim.cpp:694-695 or 657)
-  const bool serial = !gptj && !m->hp.use_parallel_residual;
+  // fc_out; a long prompt joins the residual in its epilogue (vsim.cpp:694-695 or 657), except
+  // BLOOM's, whose residual is cur2
   G2Epi ej;
   ej.res = m->inpL;
   ej.res_a = serial ? nullptr : m->attn;
-  const bool join_epi = g2;
-  bool joined = false;
-  RC(mm(m, L.wproj, E, F, m->fch, N, m->xq3, m->xd3, true, L.bproj, join_epi ? m->inpL : m->ff, nk, X.b, nullptr,
-        nullptr, &joined, join_epi ? &ej : nullptr));
-  if (joined != join_epi) {
+  const bool join_epi = g2 && !keep_joined;
+  Product fo{.w = w4_view(L.wproj, E, F), .x = m->fch, .xq = m->xq3, .xd = m->xd3, .quantize = true, .bias = L.bproj,
+             .y = join_epi ? m->inpL : m->ff, .x16 = B.xb, .epi = join_epi ? &ej : nullptr};
+  RC(B.mm(fo));
+  if (fo.fused != join_epi) {
     set_error("prompt layer: residual epilogue not taken");
     return VSIM_EINVAL;
   }
-  if (!joined) {
+  if (keep_joined) {  // inpL = ff + inpFF
+    VSIM_HIP(hipMemcpyAsync(m->inpL, m->cur2, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
+    RC(launch_add_bias(m->inpL, m->ff, N * E, 1, s)); ++nk;
+  } else if (!join_epi) {
     RC(launch_add_residual(m->inpL, m->attn, m->ff, N * E, serial ? 1 : 0, s));
     ++nk;
   }
@@ -822,14 +836,13 @@ bool fast_decode_ok(const vsim_model *m) {
   const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H;
   const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
   return d % 32 == 0 && d <= 256 && E <= 8192 && E % 128 == 0 &&
-         (m->arch == VSIM_ARCH_GPTJ || (m->arch == VSIM_ARCH_GPTNEOX && m->hp.use_parallel_residual == 1)) &&
-         (m->arch == VSIM_ARCH_GPTJ || m->hp.n_rot <= 32) && 2 * H * nch <= 4096 &&
+         m->gd.residual == RES_PARALLEL && (m->gd.rotary == ROT_GPTJ || m->hp.n_rot <= 32) && 2 * H * nch <= 4096 &&
          nch <= FD_MAXCH;  // (launch_fast_tail's limit: a longer context takes the exact step)
 }
 
 int enqueue_decode_fast(vsim_model *m, int &nk) {
   const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E, V = m->hp.n_vocab;
-  const bool gptj = m->arch == VSIM_ARCH_GPTJ;
+  const GraphDesc &G = m->gd;
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
@@ -853,17 +866,17 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     P.lnx = R[cur];
     P.lnw[0] = L.ln1_w;
     P.lnb[0] = L.ln1_b;
-    P.lnw[1] = gptj ? L.ln1_w : L.ln2_w;
-    P.lnb[1] = gptj ? L.ln1_b : L.ln2_b;
+    P.lnw[1] = G.two_norms ? L.ln2_w : L.ln1_w;
+    P.lnb[1] = G.two_norms ? L.ln2_b : L.ln1_b;
     P.xq[0] = q1;
     P.xd[0] = d1;
-    P.xq[1] = gptj ? q1 : m->xq2;
-    P.xd[1] = gptj ? d1 : d2;
+    P.xq[1] = G.two_norms ? m->xq2 : q1;
+    P.xd[1] = G.two_norms ? d2 : d1;
     P.nj = 4;
     P.j[0] = FastJob{w4_view(L.wfc, F, E), L.bfc, nullptr, FE_GELU_Q, 1};
-    P.j[1] = FastJob{w4_view(L.wq, E, E), gptj ? nullptr : L.bq, m->Qb, FE_ROPE_Q, 0};
-    P.j[2] = FastJob{w4_view(L.wk, E, E), gptj ? nullptr : L.bk, m->kcache + loff, FE_ROPE_K, 0};
-    P.j[3] = FastJob{w4_view(L.wv, E, E), gptj ? nullptr : L.bv, m->vcache + loff, FE_V, 0};
+    P.j[1] = FastJob{w4_view(L.wq, E, E), G.qkvo_bias ? L.bq : nullptr, m->Qb, FE_ROPE_Q, 0};
+    P.j[2] = FastJob{w4_view(L.wk, E, E), G.qkvo_bias ? L.bk : nullptr, m->kcache + loff, FE_ROPE_K, 0};
+    P.j[3] = FastJob{w4_view(L.wv, E, E), G.qkvo_bias ? L.bv : nullptr, m->vcache + loff, FE_V, 0};
     P.gelu_tab = tab.gelu_f16;
     P.clear = m->tail_done;  // K2's per-head counters (tail_done[4h])
     P.nclear = 4 * H;
@@ -873,7 +886,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     P.cs = m->rope_cs;
     P.d = d;
     P.n_rot = m->hp.n_rot;
-    P.style = gptj ? 1 : 0;
+    P.style = G.rotary == ROT_GPTJ ? 1 : 0;
     LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (fc_in, Q, K, V)",
            w4_algo_bytes(P.j[0].w) + 3 * w4_algo_bytes(P.j[1].w));
     // fc_out split over K | attention chunks
@@ -901,7 +914,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     O.xq = T.oq_qs;
     O.xd = T.oq_d;
     O.d = d;
-    O.bo = gptj ? nullptr : L.bo;
+    O.bo = G.qkvo_bias ? L.bo : nullptr;
     O.ffp = m->fast_ffp;
     O.sf = fast_sf(m);
     O.bproj = L.bproj;
@@ -919,7 +932,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     P.xq[0] = P.xq[1] = q1;
     P.xd[0] = P.xd[1] = d1;
     P.nj = 1;
-    P.j[0] = FastJob{w4_view(m->lmh, V, E), gptj ? m->lmh_b : nullptr, m->logits, FE_STORE, 0};
+    P.j[0] = FastJob{w4_view(m->lmh, V, E), G.lmh_bias ? m->lmh_b : nullptr, m->logits, FE_STORE, 0};
     LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (lm_head)", w4_algo_bytes(P.j[0].w));
   }
   m->resid_final = R[cur];
@@ -949,14 +962,14 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
 int enqueue_decode(vsim_model *m, int &nk) {
   if (m->mode == VSIM_MODE_FAST && fast_decode_ok(m)) return enqueue_decode_fast(m, nk);
   const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E, V = m->hp.n_vocab;
-  const bool gptj = m->arch == VSIM_ARCH_GPTJ, bloom = m->arch == VSIM_ARCH_BLOOM;
-  const bool serial = bloom || (!gptj && !m->hp.use_parallel_residual);
+  const GraphDesc &G = m->gd;
+  const bool serial = G.residual != RES_PARALLEL;
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
   uint8_t *q1 = m->xq1, *q2 = m->xq2, *q3 = m->xq3, *qa = m->xqa;
   float *d1 = q4_scales(q1, E), *d2 = q4_scales(q2, E), *d3 = q4_scales(q3, F), *da = q4_scales(qa, E);
-  if (m->first && bloom) {  // word embeddings + word_embeddings_layernorm
+  if (m->first && G.emb_norm) {  // word embeddings + word_embeddings_layernorm
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->cur1, s));
     RC(launch_norm(m->cur1, m->inpL, E, 1, m->emb_w, m->emb_b, s));
     nk += 2;
@@ -1015,8 +1028,8 @@ int enqueue_decode(vsim_model *m, int &nk) {
     A.etab = tab.exp_f16;
     A.d = d;
     A.H = H;
-    A.n_rot = bloom ? 0 : m->hp.n_rot;
-    A.style = gptj ? 1 : 0;
+    A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
+    A.style = G.rotary == ROT_GPTJ ? 1 : 0;
     A.n_ctx = m->n_ctx;
     // each head over two workgroups (its KQV columns halved; the scores computed by both) in the
     // parallel-residual fused tail, where it was measured: r05, 248-token GPT-J lines 608.9 / 612.5
@@ -1033,7 +1046,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
       }
     A.scale = m->attn_scale != 0.0f ? m->attn_scale : scale;
     A.kqv_nth = m->kqv_nth;
-    A.alibi = bloom ? m->alibi : nullptr;
+    A.alibi = G.alibi ? m->alibi : nullptr;
     A.oq_qs = qa;
     A.oq_d = da;
     A.oxd = m->xda;
@@ -1082,9 +1095,9 @@ int enqueue_decode(vsim_model *m, int &nk) {
       LnQuantJob j2{R[cur], L.ln2_w, L.ln2_b, q2, d2, m->xd2};
       j2.ja = m->attn;
       j2.jab = L.bo;
-      j2.jout = bloom ? R[cur ^ 1] : nullptr;
+      j2.jout = G.residual == RES_SERIAL_JOINED ? R[cur ^ 1] : nullptr;
       LAUNCH(m, nk, launch_ln_quant(j2, nullptr, E, s), "k_ln_quant", ln_bytes(1, true));
-      if (bloom) cur ^= 1;
+      if (G.residual == RES_SERIAL_JOINED) cur ^= 1;
       // 5. fc_in (+ bias, GELU, requantize)   6. fc_out (its bias joins in the next step 1)
       GemvBatch Bi{};
       Bi.nj = 1;
@@ -1115,22 +1128,23 @@ int enqueue_decode(vsim_model *m, int &nk) {
         join_into(j2, false);
       }
       if (tail && il == m->l0) j1.ep = m->lnt_ep;  // the step's first norm advances the epoch
-      LAUNCH(m, nk, launch_ln_quant(j1, gptj ? nullptr : &j2, E, s), "k_ln_quant", ln_bytes(gptj ? 1 : 2, pending));
+      LAUNCH(m, nk, launch_ln_quant(j1, G.two_norms ? &j2 : nullptr, E, s), "k_ln_quant",
+             ln_bytes(G.two_norms ? 2 : 1, pending));
       if (pending) cur ^= 1;
     }
     ln_done = false;
     // 2. {fc_in (+bias, GELU, requantize), Q, K, V}
     GemvBatch B{};
     B.nj = 4;
-    job(B, 0, L.wfc, F, E, gptj ? m->xd1 : m->xd2, gptj ? q1 : q2, gptj ? d1 : d2, L.bfc, nullptr);
+    job(B, 0, L.wfc, F, E, G.two_norms ? m->xd2 : m->xd1, G.two_norms ? q2 : q1, G.two_norms ? d2 : d1, L.bfc, nullptr);
     B.j[0].epi = EPI_GELU_Q;
     B.j[0].gelu_tab = tab.gelu_f16;
     B.j[0].oq_qs = q3;
     B.j[0].oq_d = d3;
     B.j[0].oxd = m->xd3;
-    job(B, 1, L.wq, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bq, m->Qb);
-    job(B, 2, L.wk, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bk, m->Kb);
-    job(B, 3, L.wv, E, E, m->xd1, q1, d1, gptj ? nullptr : L.bv, m->Vb);
+    job(B, 1, L.wq, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bq : nullptr, m->Qb);
+    job(B, 2, L.wk, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bk : nullptr, m->Kb);
+    job(B, 3, L.wv, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bv : nullptr, m->Vb);
     LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
            m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (fc_in, Q, K, V)" : "k_gemv_fast_epi (fc_in, Q, K, V)",
            w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w));
@@ -1146,14 +1160,14 @@ int enqueue_decode(vsim_model *m, int &nk) {
     if (lnt) {
       TailLn N{};
       N.x = R[cur];
-      N.ab = gptj ? nullptr : L.bo;
+      N.ab = G.qkvo_bias ? L.bo : nullptr;
       N.fb = L.bproj;
       N.jout = R[cur ^ 1];
       if (il + 1 < m->l1) {  // the next layer's input norm(s)
         const LayerW &Ln = m->layers[il + 1 - m->l0];
         N.w1 = Ln.ln1_w;
         N.b1 = Ln.ln1_b;
-        if (!gptj) {
+        if (G.two_norms) {
           N.w2 = Ln.ln2_w;
           N.b2 = Ln.ln2_b;
           N.q2 = q2;
@@ -1194,7 +1208,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
     }
     pending = true;
     pend_a = m->attn;
-    pend_ab = gptj ? nullptr : L.bo;
+    pend_ab = G.qkvo_bias ? L.bo : nullptr;
     pend_fb = L.bproj;
   }
   if (m->last) {
@@ -1206,7 +1220,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
     }
     GemvBatch B{};
     B.nj = 1;
-    job(B, 0, m->lmh, V, E, m->xd1, q1, d1, gptj ? m->lmh_b : nullptr, m->logits);
+    job(B, 0, m->lmh, V, E, m->xd1, q1, d1, G.lmh_bias ? m->lmh_b : nullptr, m->logits);
     LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
            m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (lm_head)" : "k_gemv_fast_epi (lm_head)", w4_algo_bytes(B.j[0].w));
   } else if (pending) {
@@ -1278,6 +1292,14 @@ int model_create_impl(int arch, const vsim_hparams *hp, int n_ctx, int device, i
   m->l1 = layer_end;
   m->first = layer_begin == 0;
   m->last = layer_end == hp->n_layer;
+  const bool gptj = arch == VSIM_ARCH_GPTJ, bloom = arch == VSIM_ARCH_BLOOM;
+  GraphDesc &G = m->gd;
+  G.rotary = bloom ? ROT_NONE : gptj ? ROT_GPTJ : ROT_NEOX;
+  G.qkvo_bias = !gptj;
+  G.alibi = G.emb_norm = bloom;
+  G.two_norms = !gptj;
+  G.residual = bloom ? RES_SERIAL_JOINED : gptj || hp->use_parallel_residual ? RES_PARALLEL : RES_SERIAL_OLD;
+  G.lmh_bias = gptj;
   auto fail = [&](int rc) { vsim_model_free(m); return rc; };
   if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess)
     return fail(hip_fail(hipErrorUnknown, "stream"));
@@ -1487,12 +1509,10 @@ void vsim_model_free(vsim_model *m) {
 
 int vsim_model_set_tensor(vsim_model *m, const char *name, const void *host, size_t nbytes) {
   if (m->borrowed) { set_error("set_tensor: the weights belong to the graph executor"); return VSIM_EINVAL; }
-  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks, q | k | v
-    if (nbytes % 3 != 0) { set_error("set_tensor: fused qkv size"); return VSIM_EINVAL; }
-    for (int i = 0; i < 3; ++i)
-      RC(vsim_model_set_tensor(m, (n + QKV_PARTS[i]).c_str(), (const uint8_t *)host + i * (nbytes / 3), nbytes / 3));
-    return VSIM_OK;
-  }
+  if (const std::string n(name); is_fused_qkv(m, n))  // the three row blocks, q | k | v
+    return for_qkv_parts(n, nbytes, "set_tensor", [&](const char *part, size_t off, size_t nb) {
+      return vsim_model_set_tensor(m, part, (const uint8_t *)host + off, nb);
+    });
   auto it = m->slots.find(name);
   if (it == m->slots.end()) { set_error(std::string("set_tensor: unknown tensor ") + name); return VSIM_EINVAL; }
   Slot &s = it->second;
@@ -1515,12 +1535,10 @@ int vsim_model_set_tensor(vsim_model *m, const char *name, const void *host, siz
 
 int vsim_model_get_tensor(vsim_model *m, const char *name, void *host, size_t nbytes) {
   if (!m || !name || !host) { set_error("get_tensor: null argument"); return VSIM_EINVAL; }
-  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks back to back
-    if (nbytes % 3 != 0) { set_error("get_tensor: fused qkv size"); return VSIM_EINVAL; }
-    for (int i = 0; i < 3; ++i)
-      RC(vsim_model_get_tensor(m, (n + QKV_PARTS[i]).c_str(), (uint8_t *)host + i * (nbytes / 3), nbytes / 3));
-    return VSIM_OK;
-  }
+  if (const std::string n(name); is_fused_qkv(m, n))  // the three row blocks back to back
+    return for_qkv_parts(n, nbytes, "get_tensor", [&](const char *part, size_t off, size_t nb) {
+      return vsim_model_get_tensor(m, part, (uint8_t *)host + off, nb);
+    });
   auto it = m->slots.find(name);
   if (it == m->slots.end()) { set_error(std::string("get_tensor: unknown tensor ") + name); return VSIM_EINVAL; }
   const Slot &s = it->second;
@@ -1713,13 +1731,10 @@ int vsim_model_set_tensor_src(vsim_model *m, const char *name, const void *host,
     return VSIM_EINVAL;
   }
   if (m->borrowed) { set_error("set_tensor_src: the weights belong to the graph executor"); return VSIM_EINVAL; }
-  if (const std::string n(name); is_fused_qkv(m, n)) {  // the three row blocks, q | k | v
-    if (nbytes % 3 != 0) { set_error("set_tensor_src: fused qkv size"); return VSIM_EINVAL; }
-    for (int i = 0; i < 3; ++i)
-      RC(vsim_model_set_tensor_src(m, (n + QKV_PARTS[i]).c_str(), (const uint8_t *)host + i * (nbytes / 3), nbytes / 3,
-                                   src_type));
-    return VSIM_OK;
-  }
+  if (const std::string n(name); is_fused_qkv(m, n))  // the three row blocks, q | k | v
+    return for_qkv_parts(n, nbytes, "set_tensor_src", [&](const char *part, size_t off, size_t nb) {
+      return vsim_model_set_tensor_src(m, part, (const uint8_t *)host + off, nb, src_type);
+    });
   auto it = m->slots.find(name);
   if (it == m->slots.end()) { set_error(std::string("set_tensor_src: unknown tensor ") + name); return VSIM_EINVAL; }
   Slot &s = it->second;
@@ -1895,7 +1910,7 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
       m->tok_host[i] = tokens[i];
     }
     VSIM_HIP(hipMemcpyAsync(m->tok_dev, m->tok_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (m->arch == VSIM_ARCH_BLOOM) {  // word embeddings + word_embeddings_layernorm
+    if (m->gd.emb_norm) {  // word embeddings + word_embeddings_layernorm
       RC(launch_get_rows(m->wte, E, V, m->tok_dev, N, m->cur1, s));
       RC(launch_norm(m->cur1, m->inpL, E, N, m->emb_w, m->emb_b, s));
       nk += 2;
@@ -1907,7 +1922,57 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
     if (!resid_in) { set_error(std::string(who) + ": non-first stage needs resid_in"); return VSIM_EINVAL; }
     VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
   }
-  for (int il = m->l0; il < m->l1; ++il) RC(run_layer(m, il, n_past, N, nk));
+  PromptBatch B(m, N, n_past, nk);
+  for (int il = m->l0; il < m->l1; ++il) RC(run_layer(B, il));
+  return VSIM_OK;
+}
+
+// The head for `rows` rows of the residual from x: the final LayerNorm and the lm_head product
+// (+ GPT-J's bias) into out ([rows][n_vocab]).  The row count picks the product as for any prompt
+// GEMM: exact mode the row-exact GEMV / GEMM (rows independent of their neighbours); fast mode the
+// fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else quantize + GEMV.
+int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk) {
+  PromptBatch B(m, rows, 0, nk);
+  RC(B.norm(x, m->cur1, m->lnf_w, m->lnf_b, B.xa));
+  Product P{.w = w4_view(m->lmh, m->hp.n_vocab, E_(m)), .x = m->cur1, .xq = m->xq1, .xd = m->xd1, .quantize = true,
+            .bias = m->gd.lmh_bias ? m->lmh_b : nullptr, .y = out, .x16 = B.xa, .what = what};
+  return B.mm(P);
+}
+
+// The end of a call that waits for its work: the bounded waits' word read back, the stream
+// drained, the call failed if a wait gave up; then nk recorded as the call's kernels and the
+// profile's event pairs folded in.
+int finish_call(vsim_model *m, int nk) {
+  RC(spin_read(m));
+  VSIM_HIP(hipStreamSynchronize(m->stream));
+  RC(spin_check(m));
+  m->kernels_last = nk;
+  if (m->profile) RC(prof_collect(m));
+  return VSIM_OK;
+}
+
+// The opening of the whole-model single-token calls (`who`: eval_argmax, generate, eval_sample)
+// for `steps` steps from n_past (steps_name: how the range message spells it): the checks, the
+// device and the scratch, then the token and n_past into their pinned host words.  Zero steps
+// end after the range check: there is nothing to set up.
+int begin_single(vsim_model *m, const char *who, int n_past, int steps, const char *steps_name, int32_t token) {
+  const std::string w(who);
+  if (!m->first || !m->last) {
+    set_error(w + ": needs a whole-model stage with the single-token decode path");
+    return VSIM_EINVAL;
+  }
+  if (n_past < 0 || n_past + steps > m->n_ctx) {
+    set_error(w + ": n_past + " + steps_name + " exceeds n_ctx");
+    return VSIM_EINVAL;
+  }
+  if (steps == 0) return VSIM_OK;
+  VSIM_HIP(hipSetDevice(m->device));
+  RC(ensure_scratch(m, 1));
+  if (token < 0 || token >= m->hp.n_vocab) { set_error(w + ": token id out of range"); return VSIM_EINVAL; }
+  m->tok_host[0] = token;
+  m->npast_host[0] = n_past;
+  m->prof_npast = n_past;
+  m->st_npast = -1;  // the step sets the device n_past: a stage step needs a new stage_begin
   return VSIM_OK;
 }
 
@@ -1930,70 +1995,36 @@ extern "C" {
 
 int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *next_token) {
   if (!m || !next_token) { set_error("eval_argmax: null argument"); return VSIM_EINVAL; }
-  if (!m->first || !m->last) {
-    set_error("eval_argmax: needs a whole-model stage with the single-token decode path");
-    return VSIM_EINVAL;
-  }
-  if (n_past < 0 || n_past + 1 > m->n_ctx) { set_error("eval_argmax: n_past + 1 exceeds n_ctx"); return VSIM_EINVAL; }
-  VSIM_HIP(hipSetDevice(m->device));
+  RC(begin_single(m, "eval_argmax", n_past, 1, "1", token));
   const ErrScope es(m);
-  RC(ensure_scratch(m, 1));
-  if (token < 0 || token >= m->hp.n_vocab) { set_error("eval_argmax: token id out of range"); return VSIM_EINVAL; }
-  m->tok_host[0] = token;
-  m->npast_host[0] = n_past;
-  m->prof_npast = n_past;
-  m->st_npast = -1;  // this step sets the device n_past: a stage step needs a new stage_begin
   int nk = 0;
   RC(run_step(m, STEP_ARGMAX, m->graph_enabled, nk));
-  m->kernels_last = nk;
-  RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(m->stream));
-  RC(spin_check(m));
+  RC(finish_call(m, nk));
   *next_token = m->am_host[0];
-  if (m->profile) RC(prof_collect(m));
   return VSIM_OK;
 }
 
 int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, int32_t *tokens_out) {
   if (!m || !tokens_out || n_steps < 0) { set_error("generate: bad argument"); return VSIM_EINVAL; }
-  if (!m->first || !m->last) {
-    set_error("generate: needs a whole-model stage with the single-token decode path");
-    return VSIM_EINVAL;
-  }
-  if (n_past < 0 || n_past + n_steps > m->n_ctx) { set_error("generate: n_past + n_steps exceeds n_ctx"); return VSIM_EINVAL; }
+  RC(begin_single(m, "generate", n_past, n_steps, "n_steps", token));
   if (n_steps == 0) return VSIM_OK;
-  VSIM_HIP(hipSetDevice(m->device));
   const ErrScope es(m);
-  RC(ensure_scratch(m, 1));
-  if (token < 0 || token >= m->hp.n_vocab) { set_error("generate: token id out of range"); return VSIM_EINVAL; }
-  hipStream_t s = m->stream;
-  m->tok_host[0] = token;
-  m->npast_host[0] = n_past;
-  m->st_npast = -1;  // the loop advances the device n_past: a stage step needs a new stage_begin
   RC(upload_step(m));
+  int nk = 0;  // kernels of one decode step (argmax included)
   for (int i = 0; i < n_steps; ++i) {
-    int nk = 0;
+    nk = 0;
     m->prof_npast = n_past + i;
     RC(run_step(m, STEP_GEN, m->graph_enabled, nk));
-    m->kernels_last = nk;  // kernels of one decode step (argmax included)
   }
-  VSIM_HIP(hipMemcpyAsync(tokens_out, m->hist_dev + n_past, sizeof(int32_t) * n_steps, hipMemcpyDeviceToHost, s));
-  RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(s));
-  RC(spin_check(m));
-  if (m->profile) RC(prof_collect(m));
-  return VSIM_OK;
+  VSIM_HIP(hipMemcpyAsync(tokens_out, m->hist_dev + n_past, sizeof(int32_t) * n_steps, hipMemcpyDeviceToHost,
+                          m->stream));
+  return finish_call(m, nk);
 }
 
 int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t token, int32_t *next_token) {
   if (!m || !sm || !next_token) { set_error("eval_sample: null argument"); return VSIM_EINVAL; }
-  if (!m->first || !m->last) {
-    set_error("eval_sample: needs a whole-model stage with the single-token decode path");
-    return VSIM_EINVAL;
-  }
-  if (n_past < 0 || n_past + 1 > m->n_ctx) { set_error("eval_sample: n_past + 1 exceeds n_ctx"); return VSIM_EINVAL; }
+  RC(begin_single(m, "eval_sample", n_past, 1, "1", token));
   const int V = m->hp.n_vocab;
-  if (token < 0 || token >= V) { set_error("eval_sample: token id out of range"); return VSIM_EINVAL; }
   // outside the device stage's limits: the logits step and the reference's host code
   if (sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX || !(sm->temp > 0.0) ||
       !(sm->repeat_penalty > 0.0)) {
@@ -2002,13 +2033,7 @@ int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t 
     return vsim_sampler_sample_host(sm, lg.data(), V, next_token);
   }
   if (sm->top_k < 1) { set_error("eval_sample: top_k < 1"); return VSIM_EINVAL; }
-  VSIM_HIP(hipSetDevice(m->device));
   const ErrScope es(m);
-  RC(ensure_scratch(m, 1));
-  m->tok_host[0] = token;
-  m->npast_host[0] = n_past;
-  m->prof_npast = n_past;
-  m->st_npast = -1;  // this step sets the device n_past: a stage step needs a new stage_begin
   TopkParams *pb = m->sp_host;
   pb->scale = 1.0 / sm->temp;
   pb->penalty = sm->repeat_penalty;
@@ -2017,11 +2042,7 @@ int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t 
   if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
   int nk = 0;
   RC(run_step(m, STEP_SAMPLE, m->graph_enabled, nk));
-  m->kernels_last = nk;
-  RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(m->stream));
-  RC(spin_check(m));
-  if (m->profile) RC(prof_collect(m));
+  RC(finish_call(m, nk));
   return vsim_sampler_pick(sm, m->so_host->val, m->so_host->id, sm->top_k, next_token);
 }
 
@@ -2087,22 +2108,15 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
     RC(enqueue_prompt(m, n_past, tokens, N, resid_in, nk, "eval"));
     if (m->last) {
       // only the last row's logits leave the eval (vsim.cpp:736-737); rows are independent
-      const float *xl = m->inpL + (size_t)(N - 1) * E;
-      RC(launch_norm(xl, m->cur1, E, 1, m->lnf_w, m->lnf_b, s));
-      ++nk;
-      RC(mm(m, m->lmh, V, E, m->cur1, 1, m->xq1, m->xd1, true, m->arch == VSIM_ARCH_GPTJ ? m->lmh_b : nullptr,
-            m->logits, nk));
+      // (one row: the f32 norm and the GEMV in both modes)
+      RC(run_head(m, m->inpL + (size_t)(N - 1) * E, 1, m->logits, nullptr, nk));
       if (logits) VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, s));
     } else if (resid_out) {
       VSIM_HIP(hipMemcpyAsync(resid_out, m->inpL, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
     }
   }
-  RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(s));
-  RC(spin_check(m));
+  RC(finish_call(m, nk));
   if (m->last && logits) memcpy(logits, m->logit_host, sizeof(float) * V);
-  m->kernels_last = nk;
-  if (m->profile) RC(prof_collect(m));
   return VSIM_OK;
 }
 
@@ -2130,19 +2144,11 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
   // the results of all rows: N doubles, then N ints (one copy out at the end)
   double *lp_dev = (double *)m->score_out;
   int32_t *am_dev = (int32_t *)(lp_dev + N);
-  // The head, C rows at a time: final LayerNorm, lm_head, k_score_rows.  mm() picks the product
-  // as for any prompt GEMM: exact mode the row-exact GEMV / GEMM (rows independent of the chunk);
-  // fast mode the fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else the
-  // quantize + GEMV path -- so fast-mode bits may depend on C.
+  // The head, C rows at a time: final LayerNorm, lm_head, k_score_rows.  The chunk's row count
+  // picks the product (run_head), so fast-mode bits may depend on C; exact mode's do not.
   for (int r0 = 0; r0 < N; r0 += C) {
     const int c = std::min(C, N - r0);
-    const float *xl = m->inpL + (size_t)r0 * E;
-    const bool pf = m->mode == VSIM_MODE_FAST && c >= GEMM_MIN_N && m->pf_x16;
-    RC(pf ? launch_norm_f16q(xl, m->pf_x16, E, c, m->lnf_w, m->lnf_b, s)
-          : launch_norm(xl, m->cur1, E, c, m->lnf_w, m->lnf_b, s));
-    ++nk;
-    RC(mm(m, m->lmh, V, E, m->cur1, c, m->xq1, m->xd1, true, m->arch == VSIM_ARCH_GPTJ ? m->lmh_b : nullptr,
-          m->score_x, nk, pf ? m->pf_x16 : nullptr, nullptr, nullptr, nullptr, nullptr, "lm_head (score)"));
+    RC(run_head(m, m->inpL + (size_t)r0 * E, c, m->score_x, "lm_head (score)", nk));
     LAUNCH(m, nk, launch_score_rows(m->score_x, V, c, m->score_tgt + r0, lp_dev + r0, am_dev + r0, s), "k_score_rows",
            (double)c * V * sizeof(float));
     if (logits_all)
@@ -2150,13 +2156,9 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
   }
   VSIM_HIP(hipMemcpyAsync(m->score_out_host, m->score_out, (size_t)N * (sizeof(double) + sizeof(int32_t)),
                           hipMemcpyDeviceToHost, s));
-  RC(spin_read(m));
-  VSIM_HIP(hipStreamSynchronize(s));
-  RC(spin_check(m));
+  RC(finish_call(m, nk));
   if (logprob) memcpy(logprob, m->score_out_host, sizeof(double) * N);
   if (argmax) memcpy(argmax, (const double *)m->score_out_host + N, sizeof(int32_t) * N);
-  m->kernels_last = nk;
-  if (m->profile) RC(prof_collect(m));
   return VSIM_OK;
 }
 
@@ -2199,14 +2201,9 @@ int vsim_model_stage_step(vsim_model *m) {
   m->prof_npast = m->st_npast;
   int nk = 0;
   RC(run_step(m, STEP_STAGE, m->graph_enabled, nk));
-  m->kernels_last = nk;
   m->st_npast++;
-  if (m->profile) {
-    RC(spin_read(m));
-    VSIM_HIP(hipStreamSynchronize(m->stream));
-    RC(spin_check(m));
-    RC(prof_collect(m));
-  }
+  if (m->profile) return finish_call(m, nk);  // (the event pairs need the stream drained)
+  m->kernels_last = nk;
   return VSIM_OK;  // (steps run asynchronously: vsim_model_sync checks them)
 }
 
