@@ -168,6 +168,51 @@ int vsim_op_q4_quantize_w(const void *x, int src_type, int rows, int k, void *w,
  * as ggml_add does, vsim.cpp:545-547) */
 int vsim_op_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias,
                     float *y, int mode, void *stream);
+/* The batched decode step's product (k_gemm_exact_rows, exact mode only): y[n][M] for n = 1 ..
+ * VSIM_BATCH_MAX activation rows, every (weight row, activation row) the reference's chain --
+ * sumf = sumf + (f0*f2 + f1*f3) per byte pair in block order, each product and sum rounded on its
+ * own, the bias added after -- hence bit for bit vsim_op_q4_gemv(..., VSIM_MODE_EXACT) on the same
+ * operands, row by row, whatever n is.  Each weight block is fetched and dequantized once per
+ * workgroup (16 weight rows) for all n rows, where the GEMV streams the weight once per four rows.
+ * xd: vsim_op_q4_quantize's factors [n][K].  VSIM_EINVAL for n outside 1..VSIM_BATCH_MAX,
+ * K % 32 != 0 or a NULL xd.  Enqueued on stream, not synchronized. */
+#define VSIM_BATCH_MAX 32
+int vsim_op_q4_gemm_rows(const void *w, int M, int K, const float *xd, int n, const float *bias, float *y,
+                         void *stream);
+/* Process-wide choice of the product kernel of vsim_model_decode_batch: 0: vsim_op_q4_gemv's
+ * dispatch, as a short prompt's products take it (chain-GEMV jobs, four rows per launch); 1
+ * (default): k_gemm_exact_rows from B = 12 rows on, the GEMV jobs below, which is where each was
+ * measured faster (profiles/batch_decode_bench.txt); 2: k_gemm_exact_rows at every B.  All three
+ * give the same bits.  Other values select 1.  Returns the previous value. */
+int vsim_batch_set_gemm(int enable);
+/* The batched decode step's attention (k_attn_decode_batch): B rows, one new token each, every row
+ * against a KV cache and at a position of its own.  Per row and head it is the exact single-query
+ * attention of the single-token step: RoPE of q and the new k at the row's position (style 0
+ * rotate-half, 1 GPT-J pairs, n_rot = 0 none), the new K / V row written into the row's cache at
+ * that position, KQ with a double accumulator in the reference's order (ggml.c:4760-4800), scale
+ * (+ the head's ALiBi slope), soft_max with the fp16 exp table (ggml.c:5825), KQV as the
+ * sequential float chain over the keys (kqv_nth > 1: the reference pool's key runs at --threads
+ * kqv_nth), and quantize_row_q4_0 of the output row for the out-projection.  A row's results
+ * depend on that row's operands only -- not on B or on the rows beside it.  All pointers are
+ * device pointers.  Two rows must not share a cache.  d % 32 == 0, d <= 256, 1 <= B <=
+ * VSIM_BATCH_MAX, n_past[b] < n_ctx, else VSIM_EINVAL (positions are read on the device and are
+ * the caller's to keep in range).  Enqueued on stream, not synchronized. */
+typedef struct {
+  const float *q, *k, *v;   /* [B][H d]: the rows after bias, before RoPE */
+  float *const *kc;         /* [B] device array: row b's key cache [n_ctx][H d] */
+  float *const *vc;         /* [B] device array: row b's value cache */
+  const int32_t *n_past;    /* [B] device array: row b's position */
+  const double *cs;         /* RoPE table [n_ctx][n_rot/2] {cos, sin} of the angles p * 10000^(-2j/n_rot);
+                               NULL with n_rot > 0: built and uploaded by the call, which then also
+                               waits for the stream, as vsim_op_rope does */
+  const float *alibi;       /* [H] head slopes, or NULL */
+  int32_t B, d, H, n_rot, style, n_ctx, kqv_nth;
+  float scale;
+  float *out;               /* [B][H d] f32 output, or NULL */
+  void *oq;                 /* the output as Q4 SoA rows: nibbles [B][H d/32][16], then scales [B][H d/32] */
+  float *oxd;               /* [B][H d] its factors d*(q-8), pair-interleaved as vsim_op_q4_quantize's */
+} vsim_attn_batch_args;
+int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream);
 /* Long-prompt GEMM pieces (fast mode, N >= 256 inside the model): the fp16 image [M][K] of a
  * W4T32 weight (values d*(q-8) rounded to fp16), and Y[n][m] (+bias[m]) = sum_k W16[m][k] *
  * X16[n][k] on the 256 x 256-tile fp16 MFMA GEMM (K % 64 == 0; X16 [n][K] fp16). */
@@ -496,6 +541,40 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
 /* Rows per head chunk of vsim_model_eval_score, process-wide: 0 = the default, other values are
  * capped at 256.  Returns the previous value.  For tests: many ragged chunks on tiny models. */
 int vsim_score_set_chunk_rows(int rows);
+/* ---- several sequences on one model.  A model serves n_seq sequences from n_seq KV-cache slots
+ * of the shape [layers][n_ctx][n_embd] (K and V each).  Slot 0 is the cache every other entry
+ * point uses (eval, eval_argmax, generate, eval_sample, eval_score, the stage calls): those keep
+ * working on it exactly as before, captured decode graphs included.
+ * vsim_model_seq_reserve gives the model n_seq slots (a new model has one).  Growing allocates the
+ * new slots (zero-filled) and keeps the contents of the existing ones; n_seq equal to the current
+ * count does nothing; fewer is VSIM_EINVAL, as is n_seq < 1.  VSIM_ENOMEM when a slot cannot be
+ * allocated, and then the slots are as they were.  VSIM_EINVAL for a model on borrowed caches (the
+ * graph executor's) and for a pipeline stage that is not a whole model. */
+int vsim_model_seq_reserve(vsim_model *m, int n_seq);
+/* vsim_model_eval of a whole model on slot seq: N tokens at n_past, the last row's logits to
+ * `logits` (host, may be NULL).  Always the general (prompt) path, N == 1 included, because the
+ * captured single-token graphs hold slot 0's addresses; in exact mode that path gives the same
+ * bits as the captured step.  Both modes.  VSIM_EINVAL for a slot outside the reserve, a stage
+ * model, and vsim_model_eval's range errors; VSIM_ESPIN as vsim_model_eval. */
+int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *tokens, int N, float *logits);
+/* One decode step for B sequences at once: row b embeds tokens[b], attends over slot seq[b] at
+ * position n_past[b] (positions may differ from row to row) and writes that slot's cache row
+ * n_past[b].  logits (host, [B][n_vocab]) and next (host, [B]: each row's greedy id, vsim_op_argmax's
+ * conventions, taken on the device) may each be NULL; only what is asked for leaves the device.
+ * Contract (exact mode): row b of logits is bit for bit the row vsim_model_eval gives for that
+ * sequence run alone with the same history -- the reference's row -- for every B, every mix of
+ * positions and whatever else shares the batch: every product row is the reference's chain
+ * (vsim_op_q4_gemm_rows), every attention row the single-token attention on its own cache
+ * (vsim_op_attn_decode_batch), everything else is per row already.
+ * The weights stream once per step for all B rows, which is the point: B independent chains per
+ * weight row where a single sequence has one.
+ * VSIM_EINVAL for B outside 1..VSIM_BATCH_MAX, a slot outside the reserve or named twice,
+ * n_past[b] outside [0, n_ctx), a token outside the vocabulary, a model that is not a whole model,
+ * and for VSIM_MODE_FAST: fast-mode batching needs kernels and an error bound of its own and is
+ * left to a later change (run such sequences through vsim_model_eval_seq).  VSIM_ESPIN as
+ * vsim_model_eval.  The step is enqueued eagerly (no hipGraph) and waits once, at its end. */
+int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
+                            float *logits /* host [B][n_vocab] or NULL */, int32_t *next /* host [B] or NULL */);
 /* Greedy single-token decode step of a whole-model stage: eval of `token` at n_past, then
  * the argmax of the logits on the device (numpy.argmax conventions: first maximum, first
  * NaN); only the token id leaves the device.  The reference's loop samples on the host
@@ -537,7 +616,7 @@ int vsim_model_stage_begin(vsim_model *m, int n_past);
 int vsim_model_stage_step(vsim_model *m);
 int vsim_model_sync(vsim_model *m);
 /* Test support: size the scratch for n_tokens and fill every scratch buffer and the whole KV
- * cache with NaN, so that a kernel reading bytes no earlier kernel wrote shows up as a
+ * cache (every reserved sequence slot) with NaN, so that a kernel reading bytes no earlier kernel wrote shows up as a
  * changed (NaN) result.  Results of later evals must not depend on it. */
 int vsim_model_debug_poison(vsim_model *m, int n_tokens);
 /* Decode-step timing helpers for bench.py: the stream the executor launches on, and

@@ -1,0 +1,64 @@
+"""Greedy continuous batching over one model's sequence slots.
+
+generate_many() drives a model through its Model methods only (n_ctx, seq_reserve, eval_seq,
+decode_batch), so anything with those methods serves: the device model, or a stub on the CPU.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+BATCH_MAX = 32  # VSIM_BATCH_MAX: rows of one decode_batch step
+
+
+def generate_many(model, prompts, n_predict, eos=-1, n_slots=None):
+    """Greedy continuations of `prompts` (token-id lists), up to n_predict tokens each.
+
+    Prompts are admitted in order, each into the lowest free slot: the prompt is evaluated there
+    with eval_seq, and the argmax of its last row is the sequence's first token.  Then decode_batch
+    advances all live sequences by one token per step, rows in slot order.  A sequence retires when
+    it has produced `eos` (kept as its last token; -1: none), n_predict tokens, or when its next
+    token would have no position left in the context (n_ctx); its slot goes to the next waiting
+    prompt before the following step.  Returns one token list per prompt, in the prompts' order.
+
+    n_slots: how many sequences run at once (default: min(len(prompts), BATCH_MAX)); the model is
+    asked for that many slots once (seq_reserve).  In exact mode every sequence's tokens are those
+    of the sequence run alone: a row's logits do not depend on what shares its batch.
+    """
+    prompts = [list(p) for p in prompts]
+    out = [[] for _ in prompts]
+    if not prompts or n_predict <= 0:
+        return out
+    for p in prompts:
+        if not p or len(p) > model.n_ctx:
+            raise ValueError("generate_many: a prompt must have 1..n_ctx tokens")
+    n_slots = min(len(prompts), BATCH_MAX) if n_slots is None else int(n_slots)
+    if not 1 <= n_slots <= BATCH_MAX:
+        raise ValueError(f"generate_many: n_slots must be in 1..{BATCH_MAX}")
+    model.seq_reserve(n_slots)
+    free = list(range(n_slots))  # ascending: the lowest free slot is taken first
+    live = {}                    # slot -> [prompt index, n_past, last token]
+    waiting = list(range(len(prompts)))
+
+    def push(slot, i, n_past, tok):
+        """Record sequence i's new token; keep the sequence live unless it retires."""
+        out[i].append(tok)
+        if tok == eos or len(out[i]) >= n_predict or n_past >= model.n_ctx:
+            free.append(slot)
+            free.sort()
+        else:
+            live[slot] = [i, n_past, tok]
+
+    while waiting or live:
+        while waiting and free:
+            slot, i = free.pop(0), waiting.pop(0)
+            lg = model.eval_seq(slot, 0, prompts[i])
+            push(slot, i, len(prompts[i]), int(np.argmax(lg)))
+        if not live:
+            continue
+        slots = sorted(live)
+        _, nxt = model.decode_batch(slots, [live[s][1] for s in slots], [live[s][2] for s in slots],
+                                    want_logits=False)
+        for s, t in zip(slots, nxt):
+            i, n_past, _ = live.pop(s)
+            push(s, i, n_past + 1, int(t))
+    return out

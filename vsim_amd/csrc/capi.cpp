@@ -55,6 +55,57 @@ int vsim_op_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd
                     int mode, void *stream) {
   return launch_q4_gemv(w, M, K, xq, xd, n, bias, y, mode, (hipStream_t)stream);
 }
+int vsim_op_q4_gemm_rows(const void *w, int M, int K, const float *xd, int n, const float *bias, float *y,
+                         void *stream) {
+  if (!w || !y || M <= 0 || K <= 0 || K % QK) { set_error("q4_gemm_rows: bad argument"); return VSIM_EINVAL; }
+  return launch_gemm_exact_rows(w4_view(w, M, K), xd, n, bias, y, (hipStream_t)stream);
+}
+int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->d <= 0 ||
+      a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2) {
+    set_error("attn_decode_batch: bad argument");
+    return VSIM_EINVAL;
+  }
+  DevTables tab;
+  RC(tables_get(&tab));
+  if (a->n_rot > 0 && !a->cs) {  // the table built here, as vsim_op_rope does: this call then waits
+    std::vector<double2> cs((size_t)a->n_ctx * (a->n_rot / 2));
+    rope_table_host(cs.data(), a->n_ctx, a->n_rot);
+    double2 *dcs = nullptr;
+    VSIM_HIP(hipMalloc(&dcs, cs.size() * sizeof(double2)));
+    vsim_attn_batch_args b = *a;
+    b.cs = (const double *)dcs;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = hipMemcpyAsync(dcs, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess
+                 ? vsim_op_attn_decode_batch(&b, stream)
+                 : VSIM_EHIP;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = VSIM_EHIP;
+    (void)hipFree(dcs);
+    return rc;
+  }
+  const size_t nblk = (size_t)(a->B > 0 ? a->B : 0) * (a->d * a->H / QK);
+  AttnJob A{};
+  A.q = a->q;
+  A.k = a->k;
+  A.v = a->v;
+  A.cs = (const double2 *)a->cs;
+  A.etab = tab.exp_f16;
+  A.d = a->d;
+  A.H = a->H;
+  A.n_rot = a->n_rot;
+  A.style = a->style;
+  A.n_ctx = a->n_ctx;
+  A.nsplit = 1;
+  A.kqv_nth = a->kqv_nth;
+  A.scale = a->scale;
+  A.alibi = a->alibi;
+  A.oq_qs = (uint8_t *)a->oq;
+  A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
+  A.oxd = a->oxd;
+  A.out = a->out;
+  const AttnRows R{a->kc, a->vc, 0, a->n_past};
+  return launch_attn_decode_batch(A, R, a->B, a->n_ctx, (hipStream_t)stream);
+}
 int vsim_op_q4_expand_f16(const void *w, int M, int K, void *w16, void *stream) {
   if (!w || !w16 || M <= 0 || K <= 0 || K % QK) { set_error("q4_expand_f16: bad argument"); return VSIM_EINVAL; }
   return launch_w4_expand_f16(w4_view(w, M, K), w16, (hipStream_t)stream);

@@ -153,6 +153,16 @@ int launch_residual_join(const float *x, const float *a, const float *ab, const 
                          int n, hipStream_t s);
 int launch_gemv_epi(const GemvBatch &B, int mode, hipStream_t s);
 int launch_attn_decode(const AttnJob &A, int n_ctx, hipStream_t s);
+// The batched decode step's attention (k_attn_decode_batch, layer.hip): B rows, one token each,
+// every row with a KV cache and a position of its own.  A is the job of row 0 -- q, k, v, out
+// [B][E]; oq_qs [B][E/32][16], oq_d [B][E/32], oxd [B][E] (launch_q4_quantize's layout for B rows);
+// its kc / vc / npast are not used -- and row b takes kc[b] + loff, vc[b] + loff and npast + b.
+struct AttnRows {
+  float *const *kc, *const *vc;  // [B] device arrays: each row's cache base ([layers][n_ctx][E])
+  size_t loff;                   // the layer's offset into a cache, in floats
+  const int *npast;              // [B] device positions
+};
+int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s);
 // exact-mode chain GEMV (gemv_chain.hip): a batch of jobs with the GemvBatch epilogues
 int launch_gemv_chain_batch(const GemvBatch &B, hipStream_t s);
 // true when launch_gemv_chain_batch runs B as k_gemv_solo (else k_gemv_chain32)
@@ -299,6 +309,9 @@ int launch_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd,
 int launch_gemv_batch(const GemvBatch &B, int mode, hipStream_t s);
 // exact mode, N > 1 tokens: every (row, token) the reference's fp32 chain (gemm_exact.hip)
 int launch_gemm_exact(const W4 &W, const float *xd, int n, const float *bias, float *y, hipStream_t s);
+// exact mode, 1..VSIM_BATCH_MAX rows (the batched decode step): the same chains, each weight block
+// dequantized once per workgroup for all rows (gemm_rows.hip)
+int launch_gemm_exact_rows(const W4 &W, const float *xd, int n, const float *bias, float *y, hipStream_t s);
 int launch_act_repack(const void *aos, void *xq, int n, int k, hipStream_t s);
 int launch_act_unpack(const void *xq, void *aos, int n, int k, hipStream_t s);
 int launch_q4_dequant(const void *xq, int rows, int k, float *y, hipStream_t s);

@@ -152,4 +152,41 @@ int launch_attn_decode(const AttnJob &A, int n_ctx, hipStream_t s) {
   return VSIM_OK;
 }
 
+// ------------------------------------------------------------------ 3b. attention, B rows
+// The batched decode step: workgroup (hs, b) is the same head of row b -- its own cache, its own
+// position, its own slices of Q / K / V and of the Q4 output rows -- so a row's bits are those of
+// k_attn_decode on that row alone, whatever shares the launch.
+__global__ void __launch_bounds__(ATT_THREADS) k_attn_decode_batch(AttnJob A, AttnRows R) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int b = blockIdx.y, E = A.d * A.H;
+  const size_t ro = (size_t)b * E, bo = (size_t)b * (E / QK);
+  A.q += ro;
+  A.k += ro;
+  A.v += ro;
+  A.kc = R.kc[b] + R.loff;
+  A.vc = R.vc[b] + R.loff;
+  A.npast = R.npast + b;
+  A.oq_qs += bo * 16;
+  A.oq_d += bo;
+  A.oxd += ro;
+  if (A.out) A.out += ro;
+  attn_body<ATT_THREADS>(A, blockIdx.x, sm);
+}
+
+int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s) {
+  const int S = A.nsplit > 1 ? A.nsplit : 1;
+  if (A.d % 32 != 0 || A.d > 256 || A.n_ctx != n_ctx || A.d % S != 0 || (A.d / S) % QK != 0) {
+    set_error("attention: head dim must be a multiple of 32, at most 256");
+    return VSIM_EINVAL;
+  }
+  if (B < 1 || B > VSIM_BATCH_MAX || !R.kc || !R.vc || !R.npast) {
+    set_error("attn_decode_batch: 1..32 rows with their caches and positions");
+    return VSIM_EINVAL;
+  }
+  const size_t smem = (size_t)attn_lds_floats(A.d, n_ctx) * sizeof(float);
+  hipLaunchKernelGGL(k_attn_decode_batch, dim3(A.H * S, B), dim3(ATT_THREADS), smem, s, A, R);
+  VSIM_HIP(hipGetLastError());
+  return VSIM_OK;
+}
+
 }  // namespace vsim

@@ -89,6 +89,13 @@ struct GraphDesc {
   bool lmh_bias = false;   // bias on the lm_head
 };
 
+// What a batched decode step (vsim_model_decode_batch) uploads besides the tokens, in one copy:
+// each row's slot cache bases and its position
+struct BatchWords {
+  float *kc[VSIM_BATCH_MAX], *vc[VSIM_BATCH_MAX];
+  int32_t npast[VSIM_BATCH_MAX];
+};
+
 }  // namespace
 
 struct vsim_model {
@@ -113,6 +120,9 @@ struct vsim_model {
   float *alibi = nullptr;                    // BLOOM: device head slopes [n_head]
 
   float *kcache = nullptr, *vcache = nullptr;
+  // sequence slots 1.. (vsim_model_seq_reserve), each [layers][n_ctx][E] like kcache / vcache,
+  // which are slot 0
+  std::vector<float *> kslot, vslot;
   double2 *rope_cs = nullptr;
 
   // scratch, sized for n_max tokens
@@ -124,6 +134,7 @@ struct vsim_model {
   int32_t *tok_dev = nullptr;
   int32_t *tok_host = nullptr;  // pinned
   float *logit_host = nullptr;  // pinned
+  BatchWords *bw_host = nullptr, *bw_dev = nullptr;  // the batched step's per-row words (pinned, device)
   int kernels_last = 0;
 
   // fused single-token decode step (layer.hip) and its graphs
@@ -212,6 +223,10 @@ namespace {
 
 int E_(const vsim_model *m) { return m->hp.n_embd; }
 
+// the caches of sequence slot s (0: the model's own)
+float *slot_k(const vsim_model *m, int s) { return s == 0 ? m->kcache : m->kslot[s - 1]; }
+float *slot_v(const vsim_model *m, int s) { return s == 0 ? m->vcache : m->vslot[s - 1]; }
+
 // ---------------------------------------------------------------- scratch
 // Every scratch allocation for n tokens, in allocation order: where the pointer lives, its
 // bytes (0: not allocated at this n), and how it is allocated and treated.
@@ -261,6 +276,8 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->tok_dev, n * sizeof(int32_t));
   add(&m->tok_host, n * sizeof(int32_t), S_PINNED);
   add(&m->logit_host, V * f, S_PINNED);
+  add(&m->bw_host, sizeof(BatchWords), S_PINNED);
+  add(&m->bw_dev, sizeof(BatchWords));
   add(&m->xqa, q4(E), S_POISON);
   add(&m->xda, n * E * f, S_POISON);
   add(&m->inpL2, E * f, S_POISON);
@@ -650,9 +667,19 @@ struct PromptBatch {
   // scratch pf_x16: xa [N][E] norm outputs, then xb [N][F] attention / GELU outputs
   bool pf;
   void *xa, *xb;
+  // the KV cache the layers read and write ([layers][n_ctx][E] each): slot 0 unless the caller
+  // names another sequence slot (vsim_model_eval_seq)
+  float *kcache, *vcache;
+  // Batched decode step (vsim_model_decode_batch): the N rows are one token each of N sequences.
+  // rows non-null: each row's slot cache bases and position on the device, and the attention is
+  // launch_attn_decode_batch (n_past and kcache / vcache above go unused).  rows_gemm: the exact
+  // products run on k_gemm_exact_rows instead of launch_q4_gemv's dispatch (vsim_batch_set_gemm).
+  const BatchWords *rows = nullptr;
+  bool rows_gemm = false;
   PromptBatch(vsim_model *m_, int N_, int n_past_, int &nk_)
       : m(m_), N(N_), n_past(n_past_), nk(nk_), pf(m_->mode == VSIM_MODE_FAST && N_ >= GEMM_MIN_N && m_->pf_x16),
-        xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N_ * E_(m_)) : nullptr) {}
+        xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N_ * E_(m_)) : nullptr),
+        kcache(m_->kcache), vcache(m_->vcache) {}
 
   int act16(const float *x, int K, void *x16, const float *gbias, bool gelu) {
     if (!pf) return VSIM_OK;
@@ -683,6 +710,12 @@ struct PromptBatch {
       P.fused = gelu || P.epi;
       return VSIM_OK;
     }
+    // batched decode step, exact mode: every weight block dequantized once for all the rows
+    if (rows_gemm && !P.x16 && m->mode == VSIM_MODE_EXACT && N <= VSIM_BATCH_MAX) {
+      LAUNCH(m, nk, launch_gemm_exact_rows(P.w, P.xd, N, P.bias, P.y, m->stream),
+             P.what ? P.what : "k_gemm_exact_rows (batch)", w4_algo_bytes(P.w));
+      return VSIM_OK;
+    }
     LAUNCH(m, nk,
            P.x16 ? launch_gemm_f16x(P.w, P.x16, N, P.bias, P.y, m->stream)
                  : launch_q4_gemv(P.w.qs, M, K, P.xq, P.xd, N, P.bias, P.y, m->mode, m->stream),
@@ -706,7 +739,7 @@ int run_layer(PromptBatch &B, int il) {
   hipStream_t s = m->stream;
   RC(B.norm(m->inpL, m->cur1, L.ln1_w, L.ln1_b, B.xa));
   const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
-  float *kc = m->kcache + loff, *vc = m->vcache + loff;
+  float *kc = B.kcache + loff, *vc = B.vcache + loff;
   // long GPT-J prompt: RoPE and the KV-cache write (vsim.cpp:553-580) in the Q/K/V GEMMs'
   // epilogues -- K and V straight into their cache rows -- instead of a pass of their own
   const bool g2 = B.pf && N >= G2_MIN_N && E % 64 == 0;
@@ -748,18 +781,46 @@ int run_layer(PromptBatch &B, int il) {
     RC(B.mm(k));
   }
   RC(B.mm(v));
-  // KV write + RoPE (vsim.cpp:553-580; BLOOM: the write alone)
-  if (!rope_epi) {
+  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
+  if (B.rows) {
+    // batched decode step: RoPE, the cache write, KQ, softmax, KQV and the out-projection's
+    // activation quantize of every row in one launch, each row on its own cache at its own
+    // position (attn.hpp, the single-token step's head); Q4 rows in launch_q4_quantize's layout
+    DevTables tab;
+    RC(tables_get(&tab));
+    AttnJob A{};
+    A.q = m->Qb;
+    A.k = m->Kb;
+    A.v = m->Vb;
+    A.cs = m->rope_cs;
+    A.etab = tab.exp_f16;
+    A.d = d;
+    A.H = H;
+    A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
+    A.style = G.rotary == ROT_GPTJ ? 1 : 0;
+    A.n_ctx = m->n_ctx;
+    A.nsplit = 1;
+    A.scale = m->attn_scale != 0.0f ? m->attn_scale : scale;
+    A.kqv_nth = m->kqv_nth;
+    A.alibi = G.alibi ? m->alibi : nullptr;
+    A.oq_qs = m->xq2;
+    A.oq_d = (float *)(m->xq2 + (size_t)N * (E / QK) * 16);
+    A.oxd = m->xd2;
+    A.out = nullptr;
+    const AttnRows R{B.rows->kc, B.rows->vc, loff, B.rows->npast};
+    LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
+  } else if (!rope_epi) {
     RC(launch_rope_kv_write(G.rotary == ROT_GPTJ ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past,
                             G.rotary == ROT_NONE ? 0 : m->hp.n_rot, m->rope_cs, s));
     ++nk;
   }
   // attention (vsim.cpp:583-616)
   const int nkv = n_past + N;
-  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
   // (head dim 256: the attention writes the out-projection's fp16 operand itself)
   const bool attn_q16 = attn16 && B.pf && attn_prefill_quantizes(d);
-  if (attn16) {
+  if (B.rows) {
+    // (done above, the out-projection's Q4 rows included)
+  } else if (attn16) {
     // fast-mode prompt: one-pass fp16 MFMA attention (attn_prefill.hip)
     RC(launch_attn_prefill_f16(m->Qb, kc, vc, d, H, N, n_past, scale, m->attn_in, s, m->pf_scratch, m->pf_bytes,
                                kv16_epi, attn_q16 ? B.xb : nullptr));
@@ -770,7 +831,7 @@ int run_layer(PromptBatch &B, int il) {
     RC(launch_kqv(vc, E, m->kq, d, H, nkv, N, m->attn_in, 1, s, n_past)); ++nk;
   }
   if (!attn_q16) RC(B.act16(m->attn_in, E, B.xb, nullptr, false));
-  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = true,
+  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = !B.rows,
             .bias = G.qkvo_bias ? L.bo : nullptr, .y = m->attn, .x16 = B.xb};
   RC(B.mm(o));
   // fc_in (its bias goes with the GELU) reads the input norm's quantized row again, or the MLP's
@@ -1498,6 +1559,8 @@ void vsim_model_free(vsim_model *m) {
   if (m->warena) (void)hipFree(m->warena);
   if (m->kcache && !m->borrowed) (void)hipFree(m->kcache);
   if (m->vcache && !m->borrowed) (void)hipFree(m->vcache);
+  for (float *p : m->kslot) (void)hipFree(p);
+  for (float *p : m->vslot) (void)hipFree(p);
   if (m->rope_cs) (void)hipFree(m->rope_cs);
   if (m->err_dev) (void)hipFree(m->err_dev);
   if (m->err_host) (void)hipHostFree(m->err_host);
@@ -1899,8 +1962,12 @@ int run_step(vsim_model *m, StepKind kind, bool graph, int &nk, bool want_logits
 // The general path up to the head (prompt batches; scoring at every N): the embedding of
 // `tokens` (first stage) or the residual from resid_in, then this stage's layers; the rows'
 // residual ends in inpL.  `who` prefixes the error messages.
+// kc / vc: the sequence slot's caches (null: slot 0).  rows (the batched decode step): the N
+// tokens are one each of N sequences, every row on its slot at its position (n_past unused);
+// rows_gemm as PromptBatch's.
 int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in, int &nk,
-                   const char *who) {
+                   const char *who, float *kc = nullptr, float *vc = nullptr, const BatchWords *rows = nullptr,
+                   bool rows_gemm = false) {
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   if (m->first) {
@@ -1923,6 +1990,10 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
     VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
   }
   PromptBatch B(m, N, n_past, nk);
+  if (kc) B.kcache = kc;
+  if (vc) B.vcache = vc;
+  B.rows = rows;
+  B.rows_gemm = rows_gemm;
   for (int il = m->l0; il < m->l1; ++il) RC(run_layer(B, il));
   return VSIM_OK;
 }
@@ -1931,8 +2002,9 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
 // (+ GPT-J's bias) into out ([rows][n_vocab]).  The row count picks the product as for any prompt
 // GEMM: exact mode the row-exact GEMV / GEMM (rows independent of their neighbours); fast mode the
 // fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else quantize + GEMV.
-int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk) {
+int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk, bool rows_gemm = false) {
   PromptBatch B(m, rows, 0, nk);
+  B.rows_gemm = rows_gemm;
   RC(B.norm(x, m->cur1, m->lnf_w, m->lnf_b, B.xa));
   Product P{.w = w4_view(m->lmh, m->hp.n_vocab, E_(m)), .x = m->cur1, .xq = m->xq1, .xd = m->xd1, .quantize = true,
             .bias = m->gd.lmh_bias ? m->lmh_b : nullptr, .y = out, .x16 = B.xa, .what = what};
@@ -1976,6 +2048,10 @@ int begin_single(vsim_model *m, const char *who, int n_past, int steps, const ch
   return VSIM_OK;
 }
 
+std::atomic<int> g_batch_gemm{1};        // vsim_batch_set_gemm
+// from this many rows on a batched step's products run on k_gemm_exact_rows by default: below it
+// the GEMV jobs are faster (profiles/batch_decode_bench.txt)
+constexpr int BATCH_GEMM_MIN_N = 12;
 std::atomic<int> g_score_chunk_rows{0};  // vsim_score_set_chunk_rows (0: default)
 constexpr size_t SCORE_SCRATCH_BYTES = (size_t)64 << 20;
 constexpr int SCORE_MIN_ROWS = 8, SCORE_MAX_ROWS = 256;
@@ -2120,6 +2196,119 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   return VSIM_OK;
 }
 
+int vsim_batch_set_gemm(int enable) { return g_batch_gemm.exchange(enable < 0 || enable > 2 ? 1 : enable); }
+
+int vsim_model_seq_reserve(vsim_model *m, int n_seq) {
+  if (!m) { set_error("seq_reserve: null model"); return VSIM_EINVAL; }
+  if (m->borrowed || !m->first || !m->last) {
+    set_error("seq_reserve: needs a whole model that owns its KV cache");
+    return VSIM_EINVAL;
+  }
+  const int have = 1 + (int)m->kslot.size();
+  if (n_seq < have) { set_error("seq_reserve: the slots cannot shrink (have " + std::to_string(have) + ")"); return VSIM_EINVAL; }
+  if (n_seq == have) return VSIM_OK;
+  VSIM_HIP(hipSetDevice(m->device));
+  const size_t bytes = (size_t)(m->l1 - m->l0) * m->n_ctx * E_(m) * sizeof(float);
+  std::vector<float *> nk, nv;  // the new slots, handed over only when all of them exist
+  auto undo = [&] {
+    for (float *p : nk) (void)hipFree(p);
+    for (float *p : nv) (void)hipFree(p);
+  };
+  for (int i = have; i < n_seq; ++i) {
+    float *k = nullptr, *v = nullptr;
+    if (hipMalloc((void **)&k, bytes) != hipSuccess) k = nullptr;
+    if (k && hipMalloc((void **)&v, bytes) != hipSuccess) v = nullptr;
+    if (!k || !v) {
+      (void)hipGetLastError();  // the allocation's error stays with this call
+      if (k) (void)hipFree(k);
+      undo();
+      set_error("seq_reserve: KV cache alloc failed for slot " + std::to_string(i));
+      return VSIM_ENOMEM;
+    }
+    nk.push_back(k);
+    nv.push_back(v);
+    if (hipMemsetAsync(k, 0, bytes, m->stream) != hipSuccess || hipMemsetAsync(v, 0, bytes, m->stream) != hipSuccess) {
+      undo();
+      return hip_fail(hipErrorUnknown, "seq_reserve: clearing a slot");
+    }
+  }
+  if (hipStreamSynchronize(m->stream) != hipSuccess) {
+    undo();
+    return hip_fail(hipErrorUnknown, "seq_reserve: clearing the slots");
+  }
+  m->kslot.insert(m->kslot.end(), nk.begin(), nk.end());
+  m->vslot.insert(m->vslot.end(), nv.begin(), nv.end());
+  return VSIM_OK;
+}
+
+int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *tokens, int N, float *logits) {
+  if (!m) { set_error("eval_seq: null model"); return VSIM_EINVAL; }
+  if (!m->first || !m->last) { set_error("eval_seq: needs a whole model"); return VSIM_EINVAL; }
+  if (seq < 0 || seq > (int)m->kslot.size()) { set_error("eval_seq: slot outside the reserve (seq_reserve)"); return VSIM_EINVAL; }
+  if (N <= 0 || n_past < 0 || n_past + N > m->n_ctx) { set_error("eval_seq: n_past + N exceeds n_ctx"); return VSIM_EINVAL; }
+  m->st_npast = -1;  // as an eval: a stage step needs a new stage_begin
+  VSIM_HIP(hipSetDevice(m->device));
+  const ErrScope es(m);
+  RC(ensure_scratch(m, N));
+  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+  int nk = 0;
+  RC(enqueue_prompt(m, n_past, tokens, N, nullptr, nk, "eval_seq", slot_k(m, seq), slot_v(m, seq)));
+  RC(run_head(m, m->inpL + (size_t)(N - 1) * E, 1, m->logits, nullptr, nk));
+  if (logits) VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
+  RC(finish_call(m, nk));
+  if (logits) memcpy(logits, m->logit_host, sizeof(float) * V);
+  return VSIM_OK;
+}
+
+int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
+                            float *logits, int32_t *next) {
+  if (!m || !seq || !n_past || !tokens) { set_error("decode_batch: null argument"); return VSIM_EINVAL; }
+  if (!m->first || !m->last) { set_error("decode_batch: needs a whole model"); return VSIM_EINVAL; }
+  if (m->mode != VSIM_MODE_EXACT) {
+    set_error("decode_batch: exact mode only (fast-mode batching is not built: use eval_seq)");
+    return VSIM_EINVAL;
+  }
+  if (B < 1 || B > VSIM_BATCH_MAX) { set_error("decode_batch: B must be in 1..32"); return VSIM_EINVAL; }
+  const int V = m->hp.n_vocab, nslot = 1 + (int)m->kslot.size();
+  uint64_t used = 0;  // (VSIM_BATCH_MAX rows name at most that many distinct slots; slots >= 64 compared pairwise)
+  for (int b = 0; b < B; ++b) {
+    if (seq[b] < 0 || seq[b] >= nslot) { set_error("decode_batch: slot outside the reserve (seq_reserve)"); return VSIM_EINVAL; }
+    bool dup = seq[b] < 64 && ((used >> seq[b]) & 1);
+    for (int a = 0; a < b && !dup; ++a) dup = seq[a] == seq[b];
+    if (dup) { set_error("decode_batch: a slot is named twice"); return VSIM_EINVAL; }
+    if (seq[b] < 64) used |= (uint64_t)1 << seq[b];
+    if (n_past[b] < 0 || n_past[b] >= m->n_ctx) { set_error("decode_batch: n_past outside [0, n_ctx)"); return VSIM_EINVAL; }
+    if (tokens[b] < 0 || tokens[b] >= V) { set_error("decode_batch: token id out of range"); return VSIM_EINVAL; }
+  }
+  m->st_npast = -1;  // as an eval: a stage step needs a new stage_begin
+  VSIM_HIP(hipSetDevice(m->device));
+  const ErrScope es(m);
+  RC(ensure_scratch(m, B));
+  RC(ensure_score_scratch(m, B));  // the head's [B][n_vocab] rows and the greedy ids: scoring's buffers
+  hipStream_t s = m->stream;
+  for (int b = 0; b < B; ++b) {
+    m->bw_host->kc[b] = slot_k(m, seq[b]);
+    m->bw_host->vc[b] = slot_v(m, seq[b]);
+    m->bw_host->npast[b] = n_past[b];
+  }
+  VSIM_HIP(hipMemcpyAsync(m->bw_dev, m->bw_host, sizeof(BatchWords), hipMemcpyHostToDevice, s));
+  const int gm = g_batch_gemm.load();
+  const bool rows_gemm = gm == 2 || (gm == 1 && B >= BATCH_GEMM_MIN_N);
+  int nk = 0;
+  RC(enqueue_prompt(m, 0, tokens, B, nullptr, nk, "decode_batch", nullptr, nullptr, m->bw_dev, rows_gemm));
+  RC(run_head(m, m->inpL, B, m->score_x, "lm_head (batch)", nk, rows_gemm));
+  int32_t *am_dev = (int32_t *)m->score_out;
+  if (next) {
+    LAUNCH(m, nk, launch_score_rows(m->score_x, V, B, nullptr, nullptr, am_dev, s), "k_score_rows",
+           (double)B * V * sizeof(float));
+    VSIM_HIP(hipMemcpyAsync(m->score_out_host, am_dev, sizeof(int32_t) * B, hipMemcpyDeviceToHost, s));
+  }
+  if (logits) VSIM_HIP(hipMemcpyAsync(logits, m->score_x, sizeof(float) * B * V, hipMemcpyDeviceToHost, s));
+  RC(finish_call(m, nk));
+  if (next) memcpy(next, m->score_out_host, sizeof(int32_t) * B);
+  return VSIM_OK;
+}
+
 int vsim_score_set_chunk_rows(int rows) { return g_score_chunk_rows.exchange(rows > 0 ? rows : 0); }
 
 int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in,
@@ -2221,8 +2410,10 @@ int vsim_model_debug_poison(vsim_model *m, int n_tokens) {
   // ... and what the scratch table does not own
   const size_t kv = (size_t)std::max(1, m->l1 - m->l0) * m->n_ctx * E_(m) * sizeof(float);
   RC(nan_fill(m->pf_scratch, m->pf_bytes & ~(size_t)3));
-  RC(nan_fill(m->kcache, kv));
-  RC(nan_fill(m->vcache, kv));
+  for (int sl = 0; sl <= (int)m->kslot.size(); ++sl) {
+    RC(nan_fill(slot_k(m, sl), kv));
+    RC(nan_fill(slot_v(m, sl), kv));
+  }
   VSIM_HIP(hipStreamSynchronize(m->stream));
   return VSIM_OK;
 }

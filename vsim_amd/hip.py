@@ -49,7 +49,11 @@ EXPORTS = [
     "vsim_op_q4_quantize_w", "vsim_model_load_file_ex", "vsim_model_set_tensor_src", "vsim_quantize_set_chunk_rows",
     "vsim_quantize_file", "vsim_quantize_set_verbose",
     "vsim_op_logprob", "vsim_model_eval_score", "vsim_score_set_chunk_rows",
+    "vsim_op_q4_gemm_rows", "vsim_batch_set_gemm", "vsim_op_attn_decode_batch",
+    "vsim_model_seq_reserve", "vsim_model_eval_seq", "vsim_model_decode_batch",
 ]
+
+BATCH_MAX = 32  # VSIM_BATCH_MAX
 
 SRC_F32, SRC_F16 = 0, 1  # VSIM_SRC_*
 LOAD_QUANTIZE = 1        # VSIM_LOAD_QUANTIZE
@@ -130,6 +134,16 @@ class FastTailArgs(ctypes.Structure):
                 ("vc", ctypes.c_void_p), ("n_past", ctypes.c_void_p), ("d", ctypes.c_int32), ("H", ctypes.c_int32),
                 ("nchunk", ctypes.c_int32), ("scale", ctypes.c_float), ("part", ctypes.c_void_p),
                 ("hcnt", ctypes.c_void_p), ("oq", ctypes.c_void_p)]
+
+
+class AttnBatchArgs(ctypes.Structure):
+    """vsim_attn_batch_args (include/vsim_hip.h)."""
+    _fields_ = [("q", ctypes.c_void_p), ("k", ctypes.c_void_p), ("v", ctypes.c_void_p), ("kc", ctypes.c_void_p),
+                ("vc", ctypes.c_void_p), ("n_past", ctypes.c_void_p), ("cs", ctypes.c_void_p),
+                ("alibi", ctypes.c_void_p), ("B", ctypes.c_int32), ("d", ctypes.c_int32), ("H", ctypes.c_int32),
+                ("n_rot", ctypes.c_int32), ("style", ctypes.c_int32), ("n_ctx", ctypes.c_int32),
+                ("kqv_nth", ctypes.c_int32), ("scale", ctypes.c_float), ("out", ctypes.c_void_p),
+                ("oq", ctypes.c_void_p), ("oxd", ctypes.c_void_p)]
 
 
 class QuantizeStats(ctypes.Structure):
@@ -248,6 +262,12 @@ def lib():
     L.vsim_op_logprob.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.vsim_model_eval_score.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp]
     L.vsim_score_set_chunk_rows.argtypes = [ci]
+    L.vsim_op_q4_gemm_rows.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
+    L.vsim_batch_set_gemm.argtypes = [ci]
+    L.vsim_op_attn_decode_batch.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
+    L.vsim_model_seq_reserve.argtypes = [vp, ci]
+    L.vsim_model_eval_seq.argtypes = [vp, ci, ci, vp, ci, vp]
+    L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -366,6 +386,29 @@ def score_set_chunk_rows(rows: int) -> int:
     return int(lib().vsim_score_set_chunk_rows(int(rows)))
 
 
+def q4_gemm_rows(w, M, K, xd, n, bias, y, stream=None):
+    """vsim_op_q4_gemm_rows on device buffers (torch tensors): y [n][M] = the exact Q4_0 product
+    of the W4T32 weight w [M][K] with the n (1..BATCH_MAX) activation rows whose factors are xd
+    [n][K] (q4_quantize's), + bias [M] when given.  Enqueued on `stream`, not synchronized."""
+    check(lib().vsim_op_q4_gemm_rows(ptr(w), M, K, ptr(xd), n, ptr(bias), ptr(y), stream), "q4_gemm_rows")
+
+
+def batch_set_gemm(enable) -> int:
+    """Product kernel of Model.decode_batch: 0 the GEMV-job path, 1 (default) k_gemm_exact_rows from
+    the batch size on at which it was measured faster, 2 k_gemm_exact_rows always; same bits either
+    way.  Returns the previous setting."""
+    return int(lib().vsim_batch_set_gemm(int(enable)))
+
+
+def attn_decode_batch(q, k, v, kc, vc, n_past, cs, alibi, B, d, H, n_rot, style, n_ctx, kqv_nth, scale, out, oq, oxd,
+                      stream=None):
+    """vsim_op_attn_decode_batch on device buffers (torch tensors): q, k, v [B][H d]; kc, vc int64
+    tensors [B] holding each row's cache address; n_past int32 [B]; out may be None."""
+    a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), B, d, H, n_rot,
+                      style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
+    check(lib().vsim_op_attn_decode_batch(ctypes.byref(a), stream), "attn_decode_batch")
+
+
 def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,
               d=0, n_rot=0, style=0, clear=None, nclear=0, stream=None):
     """vsim_op_fast_gemv: jobs = [(w, rows, k, bias, y, epi, act)], operands torch tensors or None."""
@@ -478,6 +521,33 @@ class Model:
         check(lib().vsim_model_eval_score(self.h, n_past, ptr(tok), N, ptr(resid_in), ptr(tgt), ptr(lp), ptr(am),
                                           ptr(lg)), "score")
         return (lp, am, lg) if want_logits else (lp, am)
+
+    def seq_reserve(self, n_seq: int):
+        """Give the model n_seq KV-cache slots (slot 0 is the cache every other call uses)."""
+        check(lib().vsim_model_seq_reserve(self.h, int(n_seq)), "seq_reserve")
+
+    def eval_seq(self, seq, n_past, tokens, want_logits=True):
+        """Model.eval of `tokens` at n_past on sequence slot `seq`; the last row's logits."""
+        tok = np.ascontiguousarray(tokens, np.int32)
+        lg = np.zeros(self.n_vocab, np.float32) if want_logits else None
+        check(lib().vsim_model_eval_seq(self.h, int(seq), int(n_past), ptr(tok), int(tok.size), ptr(lg)), "eval_seq")
+        return lg
+
+    def decode_batch(self, seqs, n_past, tokens, want_logits=True):
+        """One decode step for len(seqs) sequences: row b feeds tokens[b] to slot seqs[b] at
+        position n_past[b].  Returns (logits [B][n_vocab] or None, next int32 [B]: each row's
+        greedy id, taken on the device)."""
+        sq = np.ascontiguousarray(seqs, np.int32)
+        npst = np.ascontiguousarray(n_past, np.int32)
+        tok = np.ascontiguousarray(tokens, np.int32)
+        if not (sq.size == npst.size == tok.size):
+            raise ValueError("decode_batch: one slot, position and token per row")
+        B = int(sq.size)
+        lg = np.zeros((B, self.n_vocab), np.float32) if want_logits else None
+        nxt = np.zeros(max(B, 1), np.int32)
+        check(lib().vsim_model_decode_batch(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)),
+              "decode_batch")
+        return lg, nxt[:B]
 
     def eval_argmax(self, n_past, token) -> int:
         """Greedy decode step: the next token (argmax of the logits, taken on the device)."""
