@@ -185,6 +185,30 @@ int vsim_op_q4_gemm_rows(const void *w, int M, int K, const float *xd, int n, co
  * measured faster (profiles/batch_decode_bench.txt); 2: k_gemm_exact_rows at every B.  All three
  * give the same bits.  Other values select 1.  Returns the previous value. */
 int vsim_batch_set_gemm(int enable);
+/* The fast batched decode step's product (k_gemm_fast_rows): y[n][M] = W[M][K] . q4_0(x)[n][K]
+ * (+ bias) for n = 1 .. VSIM_BATCH_MAX activation rows, every weight block fetched and unpacked once
+ * per workgroup (16 weight rows) for all n rows.  Contract: each output is bit for bit what
+ * vsim_op_q4_gemv(..., n = 1, VSIM_MODE_FAST) gives for that (weight row, activation row) alone,
+ * whatever n is and whatever rows stand beside it:
+ *   isum_b  = the exact integer dot of block b's 32 (nibble - 8) pairs (formed on the i8 matrix
+ *             core here, with v_dot8_i32_i4 there: an integer either way);
+ *   part[p] = 0.0f; for b = p, p + 16, p + 32, ... < K/32:
+ *               part[p] = fmaf(d_w[b] * d_x[b], (float)isum_b, part[p])     (p = 0 .. 15; the scale
+ *             product rounded to fp32 first; a partial with no block stays +0);
+ *   sum     = 0.0f; for p = 0 .. 15: sum += part[p];
+ *   y       = bias ? sum + bias[row] : sum.
+ * xq: vsim_op_q4_quantize's Q4 SoA rows (nibbles [n][K/32][16], then scales [n][K/32]).  The weight
+ * is W4T32 and needs no VSIM_FAST_PAD behind it; activation rows >= n are not read and y rows >= n
+ * not written.  VSIM_EINVAL for n outside 1..VSIM_BATCH_MAX, K % 32 != 0, M <= 0 or a NULL w, xq
+ * or y.  Enqueued on stream, not synchronized. */
+int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n, const float *bias, float *y,
+                              void *stream);
+/* Process-wide choice of how vsim_op_q4_gemm_fast_rows and the products of
+ * vsim_model_decode_batch_fast run: 0: one k_gemv_fast launch per row (the weight streams once per
+ * row); 1 (default): k_gemm_fast_rows from the smallest row count where it was measured faster by
+ * more than 5 % (profiles/batch_fast_bench.txt), the per-row launches below; 2: k_gemm_fast_rows at
+ * every n.  All three give the same bits.  Other values select 1.  Returns the previous value. */
+int vsim_batch_set_fast_gemm(int enable);
 /* The batched decode step's attention (k_attn_decode_batch): B rows, one new token each, every row
  * against a KV cache and at a position of its own.  Per row and head it is the exact single-query
  * attention of the single-token step: RoPE of q and the new k at the row's position (style 0
@@ -570,11 +594,25 @@ int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *token
  * weight row where a single sequence has one.
  * VSIM_EINVAL for B outside 1..VSIM_BATCH_MAX, a slot outside the reserve or named twice,
  * n_past[b] outside [0, n_ctx), a token outside the vocabulary, a model that is not a whole model,
- * and for VSIM_MODE_FAST: fast-mode batching needs kernels and an error bound of its own and is
- * left to a later change (run such sequences through vsim_model_eval_seq).  VSIM_ESPIN as
+ * and for a model in VSIM_MODE_FAST: this call is the exact step (a fast-mode batch is
+ * vsim_model_decode_batch_fast's, below).  VSIM_ESPIN as
  * vsim_model_eval.  The step is enqueued eagerly (no hipGraph) and waits once, at its end. */
 int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
                             float *logits /* host [B][n_vocab] or NULL */, int32_t *next /* host [B] or NULL */);
+/* The same step with fast-mode products, whatever vsim_model_set_mode says: the call names its
+ * numeric path.  Arguments, checks and errors are vsim_model_decode_batch's (without the mode
+ * refusal).  Every product (Q, K, V, out-projection, fc_in, fc_out, lm_head) runs on the rows' Q4_0
+ * quantization through vsim_op_q4_gemm_fast_rows' dispatch (vsim_batch_set_fast_gemm), so the
+ * weights stream once per step for all B rows; the other kernels are the exact step's.
+ * Contract: row b of logits is bit for bit the row vsim_model_eval_seq(m, seq[b], n_past[b],
+ * &tokens[b], 1, logits) gives on this model in VSIM_MODE_FAST from the same cache state, and the
+ * cache rows written are the same too -- for every B, every mix of positions and whatever else
+ * shares the batch -- so a slot may be advanced by either call in any order.  (A product row does
+ * not depend on the batch: vsim_op_q4_gemm_fast_rows' contract; neither does any other kernel's.)
+ * Fast mode's distance from the reference is that of vsim_model_eval_seq in VSIM_MODE_FAST. */
+int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                 const int32_t *tokens, float *logits /* host [B][n_vocab] or NULL */,
+                                 int32_t *next /* host [B] or NULL */);
 /* Greedy single-token decode step of a whole-model stage: eval of `token` at n_past, then
  * the argmax of the logits on the device (numpy.argmax conventions: first maximum, first
  * NaN); only the token id leaves the device.  The reference's loop samples on the host

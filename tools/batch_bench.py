@@ -14,6 +14,13 @@ today by running them in turn -- measured in the same job, from this library and
 
   python tools/batch_bench.py --out profiles/batch_decode_bench.txt --baseline-lib PATH --tree "1b11083 + this change"
   python tools/batch_bench.py --one-step 16        # for a profiler run: warm-up, then one B = 16 step
+
+--mode fast measures vsim_model_decode_batch_fast instead (vsim_batch_set_fast_gemm 2, k_gemm_fast_rows
+at every B, against 0, one k_gemv_fast launch per row), with two baselines from --baseline-lib in child
+processes: that library's exact vsim_model_decode_batch at the same B, and its fast-mode
+vsim_model_generate; then one profiled B = 32 step.
+
+  python tools/batch_bench.py --mode fast --out profiles/batch_fast_bench.txt --baseline-lib PATH --tree "..."
 """
 import argparse
 import ctypes
@@ -65,8 +72,10 @@ def baseline_child(a):
 
     ck(L.vsim_model_create(ARCH[arch_s], hpc, a.n_ctx, 0, 0, -1, ctypes.byref(h)), "create")
     ck(L.vsim_model_randomize(h, 1, 0.02), "randomize")
-    ck(L.vsim_model_set_mode(h, 0), "set_mode")
+    ck(L.vsim_model_set_mode(h, 1 if a.child_mode == "fast" else 0), "set_mode")
     ck(L.vsim_model_set_graph(h, 1), "set_graph")
+    if a.child_kind == "batch":
+        return baseline_child_batch(a, L, h, ck)
     prompt = np.arange(1, a.pos0 + 1, dtype=np.int32)
     ck(L.vsim_model_eval(h, 0, prompt.ctypes.data, a.pos0, None, None, None), "eval")
     n = a.pos1 - a.pos0
@@ -80,35 +89,144 @@ def baseline_child(a):
     print(json.dumps({"tok_s": statistics.median(runs[1:]), "runs": runs[1:]}))
 
 
-def run_baseline(a, lib):
+def baseline_child_batch(a, L, h, ck):
+    """vsim_model_decode_batch (exact mode) of the library at a.lib for every B of a.bs, timed as
+    timed_steps does: prints one JSON line {B: {"tok_s", "runs"}}."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.vsim_model_seq_reserve.argtypes = [vp, ci]
+    L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    bs = [int(b) for b in a.bs.split(",")]
+    ck(L.vsim_model_seq_reserve(h, max(bs)), "seq_reserve")
+    n, res = a.pos1 - a.pos0, {}
+    for B in bs:
+        seqs, nxt, runs = np.arange(B, dtype=np.int32), np.zeros(B, np.int32), []
+        for r in range(a.repeats):
+            tok, t0 = np.arange(3, 3 + B, dtype=np.int32), 0.0
+            for p in range(a.pos1):
+                if p == a.pos0:
+                    t0 = time.perf_counter()
+                npst = np.full(B, p, np.int32)
+                ck(L.vsim_model_decode_batch(h, B, seqs.ctypes.data, npst.ctypes.data, tok.ctypes.data, None,
+                                             nxt.ctypes.data), "decode_batch")
+                tok = nxt.copy()
+            runs.append(B * n / (time.perf_counter() - t0))
+        res[B] = {"tok_s": statistics.median(runs), "runs": runs}
+    L.vsim_model_free(h)
+    print(json.dumps(res))
+
+
+def run_baseline(a, lib, kind="generate", mode="exact"):
     cmd = [sys.executable, os.path.abspath(__file__), "--baseline-child", "--lib", lib, "--config", a.config,
            "--layers", str(a.layers), "--n-ctx", str(a.n_ctx), "--pos0", str(a.pos0), "--pos1", str(a.pos1),
-           "--repeats", str(a.repeats)]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+           "--repeats", str(a.repeats), "--child-kind", kind, "--child-mode", mode, "--bs", a.bs]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         raise RuntimeError(f"baseline run on {lib} failed:\n{r.stdout[-2000:]}{r.stderr[-2000:]}")
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def timed_steps(dm, B, pos0, pos1, timed=True):
+def timed_steps(dm, B, pos0, pos1, timed=True, fast=False):
     """Positions [0, pos1) of B sequences in slots 0..B-1; returns the seconds of [pos0, pos1)."""
     seqs = list(range(B))
     tok = [3 + b for b in range(B)]
     t0 = 0.0
+    step = dm.decode_batch_fast if fast else dm.decode_batch
     for p in range(pos1):
         if p == pos0:
             t0 = time.perf_counter()
-        _, nxt = dm.decode_batch(seqs, [p] * B, tok, want_logits=False)
+        _, nxt = step(seqs, [p] * B, tok, want_logits=False)
         tok = [int(t) for t in nxt]
     return time.perf_counter() - t0
 
 
+def main_fast(a):
+    """--mode fast: decode_batch_fast under both product paths, the parent library's exact batch and
+    fast single stream, and where one B = 32 step's time goes."""
+    from vsim_amd import hip
+    import torch
+    arch_s, hp = hparams(a.config, a.layers)
+    bs = [int(b) for b in a.bs.split(",")]
+    dm = hip.Model.create(ARCH[arch_s], hp, n_ctx=a.n_ctx)
+    dm.randomize(seed=1, std=0.02)
+    dm.set_mode(hip.MODE_FAST)
+    dm.seq_reserve(max(bs + [32]))
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    box = f"{socket.gethostname()} {torch.cuda.get_device_properties(0).gcnArchName}"
+    n = a.pos1 - a.pos0
+    say(f"# batch_bench --mode fast: {a.config} shape, {hp['n_layer']} layers, random weights (std 0.02), "
+        f"n_ctx {a.n_ctx}; box {box}; tree at {a.tree}")
+    say(f"# aggregate tok/s of decode_batch_fast over positions {a.pos0}..{a.pos1 - 1} ({n} steps, ids only, "
+        f"positions 0..{a.pos0 - 1} discarded as warm-up), wall clock round calls that end in a stream synchronize; "
+        f"median of {a.repeats} repeats, the two product paths alternating inside each repeat")
+    res = {}
+    for B in bs:
+        runs = {2: [], 0: []}
+        for r in range(a.repeats):
+            for g in ((2, 0) if r % 2 == 0 else (0, 2)):
+                hip.batch_set_fast_gemm(g)
+                runs[g].append(B * n / timed_steps(dm, B, a.pos0, a.pos1, fast=True))
+        res[B] = {g: statistics.median(v) for g, v in runs.items()}
+        say(f"B {B:2d}: k_gemm_fast_rows {res[B][2]:9.1f} tok/s   k_gemv_fast per row {res[B][0]:9.1f} tok/s   "
+            f"rows/per-row {res[B][2] / res[B][0]:5.2f}   (runs {' '.join(f'{v:.0f}' for v in runs[2])} | "
+            f"{' '.join(f'{v:.0f}' for v in runs[0])})")
+    hip.batch_set_fast_gemm(2)
+    # where the time of one B = 32 step goes (event pairs round every launch; its own pass)
+    timed_steps(dm, 32, 0, a.pos0, fast=True)
+    dm.set_profile(True)
+    dm.decode_batch_fast(list(range(32)), [a.pos0] * 32, [5] * 32, want_logits=False)
+    ks = dm.profile_kernels()
+    dm.set_profile(False)
+    tot = sum(k["ms"] for k in ks)
+    say(f"device time per kernel of one profiled B = 32 step at position {a.pos0} ({tot:.3f} ms, "
+        f"{sum(k['launches'] for k in ks)} profiled launches of {dm.info()['kernels_per_eval']} in the step; "
+        f"the unprofiled ones are the LayerNorm, quantize, GELU, join and embedding kernels):")
+    for k in sorted(ks, key=lambda k: -k["ms"]):
+        say(f"    {k['name']:<40s} {k['ms']:9.3f} ms  {100 * k['ms'] / tot:6.2f}%  {k['launches']:5d} launches")
+    prod = [k for k in ks if k["name"].startswith("k_gemm_fast_rows") or k["name"].startswith("lm_head")]
+    w, ms = sum(k["bytes"] for k in prod), sum(k["ms"] for k in prod)
+    if ms > 0:
+        say(f"    products: {w / 1e9:.3f} GB of weights in {ms:.3f} ms: {w / ms / 1e9:.2f} TB/s")
+    step_ms = 32e3 / res[32][2] if 32 in res else 0.0
+    if step_ms:
+        say(f"    wall clock of a B = 32 step (above): {step_ms:.3f} ms; profiled device time {tot:.3f} ms; the rest "
+            f"({step_ms - tot:.3f} ms) is the unprofiled kernels, launch gaps (no hipGraph) and the host round trip")
+    dm.close()
+    lib = a.baseline_lib or hip.LIB_PATH
+    who = "parent commit" if a.baseline_lib else "this library"
+    eb = {int(k): v for k, v in run_baseline(a, lib, "batch", "exact").items()}
+    fs = run_baseline(a, lib, "generate", "fast")
+    for B in bs:
+        say(f"exact vsim_model_decode_batch, {who}, B {B:2d}: {eb[B]['tok_s']:9.1f} tok/s   fast/exact "
+            f"{res[B][2] / eb[B]['tok_s']:5.2f}   (runs {' '.join(f'{x:.0f}' for x in eb[B]['runs'])})")
+    say(f"fast single stream, vsim_model_generate (hipGraph on), {who}: {fs['tok_s']:.1f} tok/s "
+        f"(runs {' '.join(f'{x:.1f}' for x in fs['runs'])})")
+    say("k_gemm_fast_rows vs k_gemv_fast per row by more than 5 %: " +
+        ", ".join(f"B {B}: {'yes' if res[B][2] > 1.05 * res[B][0] else 'no'}" for B in bs))
+    first = next((B for B in bs if res[B][2] > 1.05 * fs["tok_s"]), None)
+    say(f"smallest B whose aggregate rate exceeds the fast single stream by more than 5 %: {first}")
+    if 32 in res:
+        say(f"B = 32 condition: k_gemm_fast_rows {res[32][2]:.1f} tok/s against per-row {res[32][0]:.1f} "
+            f"({res[32][2] / res[32][0]:.2f}x) and the exact batch {eb[32]['tok_s']:.1f} ({res[32][2] / eb[32]['tok_s']:.2f}x): "
+            f"{'holds' if res[32][2] > 1.05 * max(res[32][0], eb[32]['tok_s']) else 'FAILS'}")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="exact", choices=["exact", "fast"])
+    ap.add_argument("--child-kind", default="generate", help=argparse.SUPPRESS)
+    ap.add_argument("--child-mode", default="exact", help=argparse.SUPPRESS)
     ap.add_argument("--config", default="gpt-j-6B")
     ap.add_argument("--layers", type=int, default=0, help="0: the config's own depth")
     ap.add_argument("--n-ctx", type=int, default=512)
-    ap.add_argument("--bs", default="1,2,4,8,16,32")
+    ap.add_argument("--bs", default="", help="default 1,2,4,8,16,32 (--mode fast: 1,2,4,8,12,16,24,32)")
     ap.add_argument("--pos0", type=int, default=10)
     ap.add_argument("--pos1", type=int, default=138)
     ap.add_argument("--repeats", type=int, default=3)
@@ -119,8 +237,11 @@ def main():
     ap.add_argument("--baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--lib", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    a.bs = a.bs or ("1,2,4,8,12,16,24,32" if a.mode == "fast" else "1,2,4,8,16,32")
     if a.baseline_child:
         return baseline_child(a)
+    if a.mode == "fast":
+        return main_fast(a)
 
     from vsim_amd import hip
     arch_s, hp = hparams(a.config, a.layers)

@@ -1,7 +1,7 @@
 """Greedy continuous batching over one model's sequence slots.
 
 generate_many() drives a model through its Model methods only (n_ctx, seq_reserve, eval_seq,
-decode_batch), so anything with those methods serves: the device model, or a stub on the CPU.
+decode_batch, decode_batch_fast), so anything with those methods serves: the device model, or a stub on the CPU.
 """
 from __future__ import annotations
 
@@ -10,7 +10,7 @@ import numpy as np
 BATCH_MAX = 32  # VSIM_BATCH_MAX: rows of one decode_batch step
 
 
-def generate_many(model, prompts, n_predict, eos=-1, n_slots=None):
+def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False):
     """Greedy continuations of `prompts` (token-id lists), up to n_predict tokens each.
 
     Prompts are admitted in order, each into the lowest free slot: the prompt is evaluated there
@@ -23,6 +23,10 @@ def generate_many(model, prompts, n_predict, eos=-1, n_slots=None):
     n_slots: how many sequences run at once (default: min(len(prompts), BATCH_MAX)); the model is
     asked for that many slots once (seq_reserve).  In exact mode every sequence's tokens are those
     of the sequence run alone: a row's logits do not depend on what shares its batch.
+
+    fast: the steps go through decode_batch_fast (fast-mode products, one weight pass per step for
+    all rows) instead of decode_batch.  Prompts still go through eval_seq, in the model's mode; on a
+    model in fast mode every sequence's tokens are then those of its own eval_seq loop.
     """
     prompts = [list(p) for p in prompts]
     out = [[] for _ in prompts]
@@ -56,8 +60,9 @@ def generate_many(model, prompts, n_predict, eos=-1, n_slots=None):
         if not live:
             continue
         slots = sorted(live)
-        _, nxt = model.decode_batch(slots, [live[s][1] for s in slots], [live[s][2] for s in slots],
-                                    want_logits=False)
+        step = model.decode_batch_fast if fast else model.decode_batch
+        _, nxt = step(slots, [live[s][1] for s in slots], [live[s][2] for s in slots],
+                      want_logits=False)
         for s, t in zip(slots, nxt):
             i, n_past, _ = live.pop(s)
             push(s, i, n_past + 1, int(t))

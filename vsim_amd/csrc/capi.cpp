@@ -60,6 +60,15 @@ int vsim_op_q4_gemm_rows(const void *w, int M, int K, const float *xd, int n, co
   if (!w || !y || M <= 0 || K <= 0 || K % QK) { set_error("q4_gemm_rows: bad argument"); return VSIM_EINVAL; }
   return launch_gemm_exact_rows(w4_view(w, M, K), xd, n, bias, y, (hipStream_t)stream);
 }
+int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n, const float *bias, float *y,
+                              void *stream) {
+  if (!w || !xq || !y || M <= 0 || K <= 0 || K % QK || n < 1 || n > VSIM_BATCH_MAX) {
+    set_error("q4_gemm_fast_rows: 1..32 activation rows, K a multiple of 32, w, xq and y required");
+    return VSIM_EINVAL;
+  }
+  return launch_gemm_fast_rows(w4_view(w, M, K), xq, n, bias, y, (hipStream_t)stream);
+}
+int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
   if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->d <= 0 ||
       a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2) {

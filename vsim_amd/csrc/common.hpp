@@ -312,6 +312,13 @@ int launch_gemm_exact(const W4 &W, const float *xd, int n, const float *bias, fl
 // exact mode, 1..VSIM_BATCH_MAX rows (the batched decode step): the same chains, each weight block
 // dequantized once per workgroup for all rows (gemm_rows.hip)
 int launch_gemm_exact_rows(const W4 &W, const float *xd, int n, const float *bias, float *y, hipStream_t s);
+// fast mode, 1..VSIM_BATCH_MAX rows (the fast batched decode step): k_gemv_fast's value of every
+// (weight row, activation row), bit for bit, each weight block fetched once per workgroup for all
+// rows (gemm_fast_rows.hip) -- or, by vsim_batch_set_fast_gemm, one k_gemv_fast launch per row.
+// xq: launch_q4_quantize's Q4 SoA rows
+int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
+int batch_set_fast_gemm(int enable);   // vsim_batch_set_fast_gemm; returns the old setting
+bool batch_fast_gemm_rows(int n);      // true when launch_gemm_fast_rows runs n rows on k_gemm_fast_rows
 int launch_act_repack(const void *aos, void *xq, int n, int k, hipStream_t s);
 int launch_act_unpack(const void *xq, void *aos, int n, int k, hipStream_t s);
 int launch_q4_dequant(const void *xq, int rows, int k, float *y, hipStream_t s);

@@ -676,10 +676,18 @@ struct PromptBatch {
   // products run on k_gemm_exact_rows instead of launch_q4_gemv's dispatch (vsim_batch_set_gemm).
   const BatchWords *rows = nullptr;
   bool rows_gemm = false;
-  PromptBatch(vsim_model *m_, int N_, int n_past_, int &nk_)
-      : m(m_), N(N_), n_past(n_past_), nk(nk_), pf(m_->mode == VSIM_MODE_FAST && N_ >= GEMM_MIN_N && m_->pf_x16),
+  // The products' mode: the model's, or the call's for a rows batch (decode_batch is exact,
+  // decode_batch_fast fast, whatever the model's mode).  A fast rows batch (its layers and its
+  // head) keeps the Q4 rows at every N -- never the fp16 operands of a prompt batch -- and runs
+  // its products through launch_gemm_fast_rows.
+  int mode;
+  bool fast_rows;
+  PromptBatch(vsim_model *m_, int N_, int n_past_, int &nk_, int rows_mode = -1)
+      : m(m_), N(N_), n_past(n_past_), nk(nk_),
+        pf(rows_mode < 0 && m_->mode == VSIM_MODE_FAST && N_ >= GEMM_MIN_N && m_->pf_x16),
         xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N_ * E_(m_)) : nullptr),
-        kcache(m_->kcache), vcache(m_->vcache) {}
+        kcache(m_->kcache), vcache(m_->vcache), mode(rows_mode < 0 ? m_->mode : rows_mode),
+        fast_rows(rows_mode == VSIM_MODE_FAST) {}
 
   int act16(const float *x, int K, void *x16, const float *gbias, bool gelu) {
     if (!pf) return VSIM_OK;
@@ -710,15 +718,25 @@ struct PromptBatch {
       P.fused = gelu || P.epi;
       return VSIM_OK;
     }
+    // fast batched decode step: k_gemv_fast's value of every row, on k_gemm_fast_rows (one pass of
+    // the weight for all rows) or as one launch per row (vsim_batch_set_fast_gemm): the same bits
+    if (fast_rows) {
+      if (P.x16 || N > VSIM_BATCH_MAX) { set_error("fast batched step: a product left the Q4 rows"); return VSIM_EINVAL; }
+      LAUNCH(m, nk, launch_gemm_fast_rows(P.w, P.xq, N, P.bias, P.y, m->stream),
+             P.what ? P.what : batch_fast_gemm_rows(N) ? "k_gemm_fast_rows (batch)" : "k_gemv_fast (batch, per row)",
+             w4_algo_bytes(P.w) * (batch_fast_gemm_rows(N) ? 1 : N));
+      if (!batch_fast_gemm_rows(N)) nk += N - 1;
+      return VSIM_OK;
+    }
     // batched decode step, exact mode: every weight block dequantized once for all the rows
-    if (rows_gemm && !P.x16 && m->mode == VSIM_MODE_EXACT && N <= VSIM_BATCH_MAX) {
+    if (rows_gemm && !P.x16 && mode == VSIM_MODE_EXACT && N <= VSIM_BATCH_MAX) {
       LAUNCH(m, nk, launch_gemm_exact_rows(P.w, P.xd, N, P.bias, P.y, m->stream),
              P.what ? P.what : "k_gemm_exact_rows (batch)", w4_algo_bytes(P.w));
       return VSIM_OK;
     }
     LAUNCH(m, nk,
            P.x16 ? launch_gemm_f16x(P.w, P.x16, N, P.bias, P.y, m->stream)
-                 : launch_q4_gemv(P.w.qs, M, K, P.xq, P.xd, N, P.bias, P.y, m->mode, m->stream),
+                 : launch_q4_gemv(P.w.qs, M, K, P.xq, P.xd, N, P.bias, P.y, mode, m->stream),
            P.what ? P.what : P.x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
            w4_algo_bytes(P.w));
     return VSIM_OK;
@@ -753,7 +771,7 @@ int run_layer(PromptBatch &B, int il) {
   // ... and the new keys' fp16 copies for the prompt attention (K rows, V^T columns), which
   // then converts only the cached keys before them.  (ALiBi lives in the softmax kernel only:
   // BLOOM keeps the KQ / softmax / KQV kernels in both modes.)
-  const bool attn16 = !G.alibi && m->mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
+  const bool attn16 = !B.rows && !G.alibi && B.mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
   if (attn16) RC(ensure_pf_scratch(m));
   const bool kv16_epi = rope_epi && attn16;
   G2Epi ek = er, ev;
@@ -1964,10 +1982,10 @@ int run_step(vsim_model *m, StepKind kind, bool graph, int &nk, bool want_logits
 // residual ends in inpL.  `who` prefixes the error messages.
 // kc / vc: the sequence slot's caches (null: slot 0).  rows (the batched decode step): the N
 // tokens are one each of N sequences, every row on its slot at its position (n_past unused);
-// rows_gemm as PromptBatch's.
+// rows_gemm and rows_mode (the products' mode of a rows batch; -1: the model's) as PromptBatch's.
 int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in, int &nk,
                    const char *who, float *kc = nullptr, float *vc = nullptr, const BatchWords *rows = nullptr,
-                   bool rows_gemm = false) {
+                   bool rows_gemm = false, int rows_mode = -1) {
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   if (m->first) {
@@ -1989,7 +2007,7 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
     if (!resid_in) { set_error(std::string(who) + ": non-first stage needs resid_in"); return VSIM_EINVAL; }
     VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
   }
-  PromptBatch B(m, N, n_past, nk);
+  PromptBatch B(m, N, n_past, nk, rows ? rows_mode : -1);
   if (kc) B.kcache = kc;
   if (vc) B.vcache = vc;
   B.rows = rows;
@@ -2002,8 +2020,10 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
 // (+ GPT-J's bias) into out ([rows][n_vocab]).  The row count picks the product as for any prompt
 // GEMM: exact mode the row-exact GEMV / GEMM (rows independent of their neighbours); fast mode the
 // fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else quantize + GEMV.
-int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk, bool rows_gemm = false) {
-  PromptBatch B(m, rows, 0, nk);
+// rows_mode >= 0: the head of a batched decode step in that mode (PromptBatch).
+int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk, bool rows_gemm = false,
+             int rows_mode = -1) {
+  PromptBatch B(m, rows, 0, nk, rows_mode);
   B.rows_gemm = rows_gemm;
   RC(B.norm(x, m->cur1, m->lnf_w, m->lnf_b, B.xa));
   Product P{.w = w4_view(m->lmh, m->hp.n_vocab, E_(m)), .x = m->cur1, .xq = m->xq1, .xd = m->xd1, .quantize = true,
@@ -2260,12 +2280,15 @@ int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *token
   return VSIM_OK;
 }
 
-int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
-                            float *logits, int32_t *next) {
+namespace {
+// One batched decode step with the products in `mode` (vsim_model_decode_batch: exact, on a model in
+// exact mode; vsim_model_decode_batch_fast: fast, whatever the model's mode)
+int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
+                      const int32_t *tokens, float *logits, int32_t *next) {
   if (!m || !seq || !n_past || !tokens) { set_error("decode_batch: null argument"); return VSIM_EINVAL; }
   if (!m->first || !m->last) { set_error("decode_batch: needs a whole model"); return VSIM_EINVAL; }
-  if (m->mode != VSIM_MODE_EXACT) {
-    set_error("decode_batch: exact mode only (fast-mode batching is not built: use eval_seq)");
+  if (mode == VSIM_MODE_EXACT && m->mode != VSIM_MODE_EXACT) {
+    set_error("decode_batch: exact mode only (a fast-mode batch is vsim_model_decode_batch_fast's)");
     return VSIM_EINVAL;
   }
   if (B < 1 || B > VSIM_BATCH_MAX) { set_error("decode_batch: B must be in 1..32"); return VSIM_EINVAL; }
@@ -2293,10 +2316,10 @@ int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int3
   }
   VSIM_HIP(hipMemcpyAsync(m->bw_dev, m->bw_host, sizeof(BatchWords), hipMemcpyHostToDevice, s));
   const int gm = g_batch_gemm.load();
-  const bool rows_gemm = gm == 2 || (gm == 1 && B >= BATCH_GEMM_MIN_N);
+  const bool rows_gemm = mode == VSIM_MODE_EXACT && (gm == 2 || (gm == 1 && B >= BATCH_GEMM_MIN_N));
   int nk = 0;
-  RC(enqueue_prompt(m, 0, tokens, B, nullptr, nk, "decode_batch", nullptr, nullptr, m->bw_dev, rows_gemm));
-  RC(run_head(m, m->inpL, B, m->score_x, "lm_head (batch)", nk, rows_gemm));
+  RC(enqueue_prompt(m, 0, tokens, B, nullptr, nk, "decode_batch", nullptr, nullptr, m->bw_dev, rows_gemm, mode));
+  RC(run_head(m, m->inpL, B, m->score_x, "lm_head (batch)", nk, rows_gemm, mode));
   int32_t *am_dev = (int32_t *)m->score_out;
   if (next) {
     LAUNCH(m, nk, launch_score_rows(m->score_x, V, B, nullptr, nullptr, am_dev, s), "k_score_rows",
@@ -2307,6 +2330,17 @@ int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int3
   RC(finish_call(m, nk));
   if (next) memcpy(next, m->score_out_host, sizeof(int32_t) * B);
   return VSIM_OK;
+}
+}  // namespace
+
+int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
+                            float *logits, int32_t *next) {
+  return decode_batch_impl(m, VSIM_MODE_EXACT, B, seq, n_past, tokens, logits, next);
+}
+
+int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                 const int32_t *tokens, float *logits, int32_t *next) {
+  return decode_batch_impl(m, VSIM_MODE_FAST, B, seq, n_past, tokens, logits, next);
 }
 
 int vsim_score_set_chunk_rows(int rows) { return g_score_chunk_rows.exchange(rows > 0 ? rows : 0); }

@@ -51,6 +51,7 @@ EXPORTS = [
     "vsim_op_logprob", "vsim_model_eval_score", "vsim_score_set_chunk_rows",
     "vsim_op_q4_gemm_rows", "vsim_batch_set_gemm", "vsim_op_attn_decode_batch",
     "vsim_model_seq_reserve", "vsim_model_eval_seq", "vsim_model_decode_batch",
+    "vsim_op_q4_gemm_fast_rows", "vsim_batch_set_fast_gemm", "vsim_model_decode_batch_fast",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -268,6 +269,9 @@ def lib():
     L.vsim_model_seq_reserve.argtypes = [vp, ci]
     L.vsim_model_eval_seq.argtypes = [vp, ci, ci, vp, ci, vp]
     L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.vsim_op_q4_gemm_fast_rows.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
+    L.vsim_batch_set_fast_gemm.argtypes = [ci]
+    L.vsim_model_decode_batch_fast.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -398,6 +402,21 @@ def batch_set_gemm(enable) -> int:
     the batch size on at which it was measured faster, 2 k_gemm_exact_rows always; same bits either
     way.  Returns the previous setting."""
     return int(lib().vsim_batch_set_gemm(int(enable)))
+
+
+def q4_gemm_fast_rows(w, M, K, xq, n, bias, y, stream=None):
+    """vsim_op_q4_gemm_fast_rows on device buffers (torch tensors): y [n][M] = the fast-mode Q4_0
+    product of the W4T32 weight w [M][K] with the n (1..BATCH_MAX) activation rows xq (q4_quantize's
+    Q4 SoA rows), + bias [M] when given; each value bit for bit q4_gemv's (n = 1, MODE_FAST) of
+    that row alone.  Enqueued on `stream`, not synchronized."""
+    check(lib().vsim_op_q4_gemm_fast_rows(ptr(w), M, K, ptr(xq), n, ptr(bias), ptr(y), stream), "q4_gemm_fast_rows")
+
+
+def batch_set_fast_gemm(enable) -> int:
+    """How q4_gemm_fast_rows and Model.decode_batch_fast run their products: 0 one k_gemv_fast
+    launch per row, 1 (default) k_gemm_fast_rows from the row count on at which it was measured
+    faster, 2 k_gemm_fast_rows always; same bits either way.  Returns the previous setting."""
+    return int(lib().vsim_batch_set_fast_gemm(int(enable)))
 
 
 def attn_decode_batch(q, k, v, kc, vc, n_past, cs, alibi, B, d, H, n_rot, style, n_ctx, kqv_nth, scale, out, oq, oxd,
@@ -537,16 +556,24 @@ class Model:
         """One decode step for len(seqs) sequences: row b feeds tokens[b] to slot seqs[b] at
         position n_past[b].  Returns (logits [B][n_vocab] or None, next int32 [B]: each row's
         greedy id, taken on the device)."""
+        return self._decode_batch(lib().vsim_model_decode_batch, "decode_batch", seqs, n_past, tokens, want_logits)
+
+    def decode_batch_fast(self, seqs, n_past, tokens, want_logits=True):
+        """decode_batch with fast-mode products, whatever the model's mode: every row bit for bit
+        eval_seq's row of that sequence on this model in MODE_FAST.  Same return shape."""
+        return self._decode_batch(lib().vsim_model_decode_batch_fast, "decode_batch_fast", seqs, n_past, tokens,
+                                  want_logits)
+
+    def _decode_batch(self, fn, who, seqs, n_past, tokens, want_logits):
         sq = np.ascontiguousarray(seqs, np.int32)
         npst = np.ascontiguousarray(n_past, np.int32)
         tok = np.ascontiguousarray(tokens, np.int32)
         if not (sq.size == npst.size == tok.size):
-            raise ValueError("decode_batch: one slot, position and token per row")
+            raise ValueError(f"{who}: one slot, position and token per row")
         B = int(sq.size)
         lg = np.zeros((B, self.n_vocab), np.float32) if want_logits else None
         nxt = np.zeros(max(B, 1), np.int32)
-        check(lib().vsim_model_decode_batch(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)),
-              "decode_batch")
+        check(fn(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)), who)
         return lg, nxt[:B]
 
     def eval_argmax(self, n_past, token) -> int:
