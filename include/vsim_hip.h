@@ -353,6 +353,29 @@ int vsim_op_attn_prefill(const float *Q, const float *kc, const float *vc, int d
  * d*(q-8) as fp16 -- what vsim_op_act_quant_f16 makes of vsim_op_attn_prefill's out. */
 int vsim_op_attn_prefill_q16(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
                              float scale, void *out16, void *stream);
+/* The fp16 scratch of the prompt attention for nk = n_past + N keys of width E = d*H: *bytes its
+ * size, K16[key][E] (row-major, as the cache) at its start, Vt16[h][dim][*ldt] at half offset
+ * *vt_off (each head's V transposed; *ldt = nk rounded up to the 64-key tile, the columns
+ * [nk, *ldt) zero).  Within each group of 16 keys V^T holds them in the order 0-3, 8-11, 4-7,
+ * 12-15 (the middle quads swapped).  Any of the three outputs may be NULL. */
+int vsim_op_attn_prefill_layout(int E, int nk, size_t *bytes, size_t *vt_off, int *ldt);
+/* vsim_op_attn_prefill / _q16 (out16 != NULL: d = 256, out unused) on the caller's scratch of at
+ * least that size, as the model's prompt layer calls it: the kernel that fills the scratch from
+ * kc / vc runs first and the copies stay there afterwards.  fresh != 0: the new keys
+ * [n_past, n_past + N) are already in the scratch (vsim_op_gemm_q4_256_h16 put them there) and
+ * only the cached keys before n_past are converted, the V^T padding zeroed. */
+int vsim_op_attn_prefill_scratch(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
+                                 float scale, float *out, void *out16, void *scratch, size_t scratch_bytes, int fresh,
+                                 void *stream);
+/* vsim_op_gemm_q4_256 (plain or RoPE epilogue) that also leaves the fp16 rounding of every
+ * y[n][m] in the prompt attention's scratch, as the model's K and V projections of a long GPT-J
+ * prompt do: with cs (RoPE, the K projection) row-major at h16[(p0 + n) * M + m], h16_t = 0;
+ * without cs (the V projection) transposed at h16[m * h16_ld + pos(p0 + n)], h16_t != 0 and
+ * h16_ld >= p0 + n, pos the key order of vsim_op_attn_prefill_layout.  Nothing else of h16 is
+ * written.  M % 4 == 0. */
+int vsim_op_gemm_q4_256_h16(const void *w, int M, int K, const void *x16, int n, const float *bias, float *y,
+                            const double *cs, int d, int n_rot, int p0, void *h16, int h16_ld, int h16_t,
+                            void *stream);
 /* The long-prompt GEMM (vsim_op_gemm_q4_256, the model's N >= 256 path) splits the K range of
  * grids with fewer 256 x 256 tiles than CUs between two workgroups (stream-K: every CU busy, the
  * two partial sums added once; a different summation order than one pass, same per-element
@@ -365,6 +388,10 @@ int vsim_gemm_set_streamk(int enable);
  * per-element bound as vsim_op_gemm_q4_256 with cs. */
 int vsim_op_gemm_q4_256_pair(const void *w0, const void *w1, int M, int K, const void *x16, int n, float *y0, float *y1,
                              const double *cs, int d, int n_rot, int p0, void *stream);
+/* The same launch with the second weight's row-major fp16 copy (vsim_op_gemm_q4_256_h16 with cs),
+ * as the model's paired Q / K launch passes it: h16_1[(p0 + n) * M + m] = fp16(y1[n][m]). */
+int vsim_op_gemm_q4_256_pair_h16(const void *w0, const void *w1, int M, int K, const void *x16, int n, float *y0,
+                                 float *y1, const double *cs, int d, int n_rot, int p0, void *h16_1, void *stream);
 /* mode 0: the model runs its prompt Q and K projections as two launches; 1 (default): one
  * paired launch, its remainder past whole rounds of the CUs split as above; 2: paired, whole
  * tiles only.  Process-wide; returns the previous setting. */

@@ -270,6 +270,44 @@ int vsim_op_attn_prefill_q16(const float *Q, const float *kc, const float *vc, i
   return launch_attn_prefill_f16(Q, kc, vc, d, H, N, n_past, scale, nullptr, (hipStream_t)stream, nullptr, 0, false,
                                  out16);
 }
+int vsim_op_attn_prefill_layout(int E, int nk, size_t *bytes, size_t *vt_off, int *ldt) {
+  if (E <= 0 || nk <= 0) { set_error("attn_prefill_layout: bad argument"); return VSIM_EINVAL; }
+  if (bytes) *bytes = attn_prefill_scratch(E, nk);
+  if (vt_off) *vt_off = (size_t)(attn_prefill_vt16(nullptr, E, nk) - attn_prefill_k16(nullptr, E, nk));
+  if (ldt) *ldt = attn_prefill_ldt(nk);
+  return VSIM_OK;
+}
+int vsim_op_attn_prefill_scratch(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
+                                 float scale, float *out, void *out16, void *scratch, size_t scratch_bytes, int fresh,
+                                 void *stream) {
+  // (the launcher allocates its own when the caller's is too small: here that is an error)
+  if (!Q || !kc || !vc || (!out && !out16) || d <= 0 || H <= 0 || N <= 0 || n_past < 0 || !scratch ||
+      scratch_bytes < attn_prefill_scratch(d * H, n_past + N)) {
+    set_error("attn_prefill_scratch: bad argument (scratch smaller than vsim_op_attn_prefill_layout's bytes?)");
+    return VSIM_EINVAL;
+  }
+  return launch_attn_prefill_f16(Q, kc, vc, d, H, N, n_past, scale, out16 ? nullptr : out, (hipStream_t)stream, scratch,
+                                 scratch_bytes, fresh != 0, out16);
+}
+int vsim_op_gemm_q4_256_h16(const void *w, int M, int K, const void *x16, int n, const float *bias, float *y,
+                            const double *cs, int d, int n_rot, int p0, void *h16, int h16_ld, int h16_t,
+                            void *stream) {
+  if (!w || !x16 || !y || !h16 || M <= 0 || K <= 0 || K % QK || p0 < 0) {
+    set_error("gemm_q4_256_h16: bad argument");
+    return VSIM_EINVAL;
+  }
+  G2Epi e;
+  if (cs) {
+    e.cs = (const double2 *)cs;
+    e.d = d;
+    e.n_rot = n_rot;
+  }
+  e.p0 = p0;
+  e.h16 = (_Float16 *)h16;
+  e.h16_ld = h16_ld;
+  e.h16_t = h16_t;
+  return launch_gemm_q4_256(w4_view(w, M, K), x16, n, bias, y, (hipStream_t)stream, nullptr, &e);
+}
 // ---- the fast decode step's launches (fast_decode.hip) on caller buffers.  The launchers
 // check the shapes the kernels stage in LDS; the checks here are the ones the model's own
 // shapes make unnecessary (null operands, whole tiles where a kernel writes all 32 rows).
@@ -395,6 +433,21 @@ int vsim_op_gemm_q4_256_pair(const void *w0, const void *w1, int M, int K, const
   e.n_rot = n_rot;
   e.p0 = p0;
   return launch_gemm_q4_256_pair(w4_view(w0, M, K), w4_view(w1, M, K), x16, n, y0, y1, e, e, (hipStream_t)stream);
+}
+int vsim_op_gemm_q4_256_pair_h16(const void *w0, const void *w1, int M, int K, const void *x16, int n, float *y0,
+                                 float *y1, const double *cs, int d, int n_rot, int p0, void *h16_1, void *stream) {
+  if (!w0 || !w1 || !x16 || !y0 || !y1 || !cs || !h16_1 || M <= 0 || K <= 0 || K % QK || p0 < 0 || n <= 0) {
+    set_error("gemm_q4_256_pair_h16: bad argument");
+    return VSIM_EINVAL;
+  }
+  G2Epi e0;
+  e0.cs = (const double2 *)cs;
+  e0.d = d;
+  e0.n_rot = n_rot;
+  e0.p0 = p0;
+  G2Epi e1 = e0;  // (as run_layer's er / ek)
+  e1.h16 = (_Float16 *)h16_1;
+  return launch_gemm_q4_256_pair(w4_view(w0, M, K), w4_view(w1, M, K), x16, n, y0, y1, e0, e1, (hipStream_t)stream);
 }
 int vsim_op_norm_f16q(const float *x, int k, int rows, const float *w, const float *b, void *x16, void *stream) {
   return launch_norm_f16q(x, x16, k, rows, w, b, (hipStream_t)stream);

@@ -52,6 +52,8 @@ EXPORTS = [
     "vsim_op_q4_gemm_rows", "vsim_batch_set_gemm", "vsim_op_attn_decode_batch",
     "vsim_model_seq_reserve", "vsim_model_eval_seq", "vsim_model_decode_batch",
     "vsim_op_q4_gemm_fast_rows", "vsim_batch_set_fast_gemm", "vsim_model_decode_batch_fast",
+    "vsim_op_attn_prefill_layout", "vsim_op_attn_prefill_scratch", "vsim_op_gemm_q4_256_h16",
+    "vsim_op_gemm_q4_256_pair_h16",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -199,6 +201,10 @@ def lib():
     L.vsim_gemm_set_tile_order.argtypes = [ci]
     L.vsim_op_gemm_q4_256_pair.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp]
     L.vsim_op_norm_f16q.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+    L.vsim_op_attn_prefill_layout.argtypes = [ci, ci, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(ci)]
+    L.vsim_op_attn_prefill_scratch.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, vp, sz, ci, vp]
+    L.vsim_op_gemm_q4_256_h16.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp]
+    L.vsim_op_gemm_q4_256_pair_h16.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp]
     L.vsim_op_tables.argtypes = [vp, vp]
     L.vsim_op_fast_gemv.argtypes = [ctypes.POINTER(FastGemvArgs), vp]
     L.vsim_op_fast_tail.argtypes = [ctypes.POINTER(FastTailArgs), vp]
