@@ -306,6 +306,40 @@ int vsim_op_argmax(const float *x, int n, int32_t *out, void *stream);
 #define VSIM_WINDOW_MAX 1024
 int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale, double repeat_penalty, int k,
                  double *val, int32_t *id, void *stream);
+/* vsim_op_topk for B logits rows in one launch (k_sample_topk_rows), every row with parameters of
+ * its own: row b reads x + b * ldx (f32, ldx >= n, so rows need 4-byte alignment only) and the
+ * device block pb[b], and writes out[b].val[0:k_b], out[b].id[0:k_b].
+ * Contract: row b's k_b (value, id) pairs are bit for bit what vsim_op_topk gives for that row
+ * alone with pb[b]'s win[0:nw], scale, penalty and k -- the same candidate formula, the same
+ * (value, lower id first) total order, so the same tie rule.  A row's result does not depend on
+ * B, on its index in the batch or on the other rows: the rows share no state (each hands off
+ * through its own block of the workspace), and within a row the total order makes the result
+ * independent of how the row is split over waves and workgroups.  Entries of out[b] past k_b are
+ * not written.
+ * The parameter blocks live on the device and are read when the kernel runs; it clamps k to
+ * 1..VSIM_TOPK_MAX and nw to 0..VSIM_WINDOW_MAX and stays in bounds and terminates for any block
+ * contents (k > n: the entries past n repeat id n - 1).  Callers that want errors check on the
+ * host, as vsim_model_decode_batch_sample does.  NaN logits: as vsim_op_topk, per row.
+ * VSIM_EINVAL for B outside 1..VSIM_BATCH_MAX, n < 1, ldx < n or a NULL pointer.
+ * The workspace (B blocks) is the library's, one per (device, stream), every block's counter zero
+ * between launches: calls on one stream may follow each other, and vsim_op_topk, without a
+ * synchronize. */
+typedef struct vsim_topk_params {
+  double scale, penalty; /* 1 / temp; the repetition penalty */
+  int32_t k, nw;         /* candidates wanted; ids in win */
+  int32_t win[VSIM_WINDOW_MAX];
+} vsim_topk_params;
+typedef struct vsim_topk_out {
+  double val[VSIM_TOPK_MAX];
+  int32_t id[VSIM_TOPK_MAX];
+} vsim_topk_out;
+int vsim_op_topk_rows(const float *x, int ldx, int n, int B, const vsim_topk_params *pb /* device [B] */,
+                      vsim_topk_out *out /* device [B] */, void *stream);
+/* Workgroups per row of k_sample_topk_rows, process-wide: 0 (default) = as many as
+ * k_sample_topk's (one per 1024 ids, at most 64) while all rows' together stay within 256, else
+ * 256 / B; 1..64 = at most that many.  Same results either way (the contract above); for tests
+ * and measurements.  Returns the previous setting. */
+int vsim_topk_rows_set_wg(int per_row);
 /* Scoring: the log-probability a logits row gives one token, and the row's greedy id, for R rows
  * x[R][V] (f32, row stride V, so any 4-byte alignment) in one launch (k_score_rows, score.hip).
  * Per row i, with m the row's maximum (a float, exact) and t = target[i]:
@@ -640,6 +674,37 @@ int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int3
 int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
                                  const int32_t *tokens, float *logits /* host [B][n_vocab] or NULL */,
                                  int32_t *next /* host [B] or NULL */);
+/* The batched step, sampled: vsim_model_decode_batch (mode = VSIM_MODE_EXACT) or
+ * vsim_model_decode_batch_fast (VSIM_MODE_FAST) up to the head, then row b's candidate stage with
+ * samplers[b]'s window, k, temperature and penalty -- all rows in one k_sample_topk_rows launch
+ * on the device logits -- one copy of the B candidate lists (768 bytes each) to the host, and
+ * after the step's single synchronize vsim_sampler_pick per row, in row order, into next[b].
+ * No logits row leaves the device.
+ * A sampler outside the device stage's limits (top_k > VSIM_TOPK_MAX or > n_vocab, repeat_last_n
+ * > VSIM_WINDOW_MAX, temp <= 0, repeat_penalty <= 0) takes the host path for its row only: that
+ * row's logits are copied out and go through vsim_sampler_sample_host; the other rows stay on the
+ * device path.  vsim_sampler_stats tells which ran.
+ * Contract, exact mode: next[b] and samplers[b]'s state afterwards (window, generator, counts)
+ * are those of vsim_model_eval_sample(m, samplers[b], n_past[b], tokens[b]) on that sequence
+ * alone with the same history -- the reference's token wherever the candidates are distinct (tie
+ * rule: vsim_op_topk).  Fast mode: those of vsim_model_eval_seq on this model in VSIM_MODE_FAST,
+ * vsim_op_topk on its logits row and vsim_sampler_pick, on the same cache.  Both follow from the
+ * logits rows being batch-independent already (the two calls above) and vsim_op_topk_rows' rows
+ * being so too.
+ * Checks and errors: those of the call the mode names (the exact step refuses a model in
+ * VSIM_MODE_FAST), and VSIM_EINVAL for another mode value, a NULL sampler or `next`, a sampler
+ * named twice (its generator would serve two sequences) and top_k < 1.  Nothing is enqueued and
+ * no sampler is touched when a check fails. */
+int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
+                                   const int32_t *tokens, vsim_sampler *const *samplers /* [B] */,
+                                   int32_t *next /* host [B] */);
+/* Slot fork: cache rows [0, n_tokens) of K and V of every layer go from slot src to slot dst
+ * (device to device on the model's stream, one strided copy each; ordered with the steps before
+ * and after it, not synchronized).  A slot holds nothing but these rows, so dst then continues
+ * any sequence whose first n_tokens tokens are src's: evaluate a prompt once, sample n
+ * continuations.  Slot 0 may be either side.  VSIM_EINVAL for a slot outside the reserve,
+ * dst == src, n_tokens outside 1..n_ctx, a model on borrowed caches or a pipeline stage. */
+int vsim_model_seq_copy(vsim_model *m, int dst, int src, int n_tokens);
 /* Greedy single-token decode step of a whole-model stage: eval of `token` at n_past, then
  * the argmax of the logits on the device (numpy.argmax conventions: first maximum, first
  * NaN); only the token id leaves the device.  The reference's loop samples on the host

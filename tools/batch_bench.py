@@ -21,6 +21,14 @@ processes: that library's exact vsim_model_decode_batch at the same B, and its f
 vsim_model_generate; then one profiled B = 32 step.
 
   python tools/batch_bench.py --mode fast --out profiles/batch_fast_bench.txt --baseline-lib PATH --tree "..."
+
+--sample measures vsim_model_decode_batch_sample in both modes (one sampler per row: top_k 20, top_p
+0.95, temp 0.85, repeat_last_n 64, repeat_penalty 1.3, seeds 1..B) against the greedy step of the same
+library and against what the parent commit offers for sampled batches: its decode_batch /
+decode_batch_fast with the [B][n_vocab] logits copied out and vsim_sampler_sample_host per row, run
+from --baseline-lib in a child process.
+
+  python tools/batch_bench.py --sample --out profiles/batch_sample_bench.txt --baseline-lib PATH --tree "..."
 """
 import argparse
 import ctypes
@@ -76,6 +84,8 @@ def baseline_child(a):
     ck(L.vsim_model_set_graph(h, 1), "set_graph")
     if a.child_kind == "batch":
         return baseline_child_batch(a, L, h, ck)
+    if a.child_kind == "sample":
+        return baseline_child_sample(a, L, h, ck)
     prompt = np.arange(1, a.pos0 + 1, dtype=np.int32)
     ck(L.vsim_model_eval(h, 0, prompt.ctypes.data, a.pos0, None, None, None), "eval")
     n = a.pos1 - a.pos0
@@ -113,6 +123,133 @@ def baseline_child_batch(a, L, h, ck):
         res[B] = {"tok_s": statistics.median(runs), "runs": runs}
     L.vsim_model_free(h)
     print(json.dumps(res))
+
+
+SAMPLE_PARAMS = dict(top_k=20, top_p=0.95, temp=0.85, repeat_last_n=64, repeat_penalty=1.3)  # interface.py's
+
+
+def baseline_child_sample(a, L, h, ck):
+    """Sampled batches as the library at a.lib allows them without a sampled batched step: its
+    decode_batch (exact) and decode_batch_fast with all B logits rows copied to the host, then
+    vsim_sampler_sample_host per row.  Prints one JSON line {mode: {B: {"tok_s", "runs"}}}."""
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.vsim_model_seq_reserve.argtypes = [vp, ci]
+    for f in (L.vsim_model_decode_batch, L.vsim_model_decode_batch_fast):
+        f.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.vsim_sampler_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.vsim_sampler_sample_host.argtypes = [vp, vp, ci, vp]
+    L.vsim_sampler_free.argtypes = [vp]
+    bs = [int(b) for b in a.bs.split(",")]
+    ck(L.vsim_model_seq_reserve(h, max(bs)), "seq_reserve")
+    _, hp = hparams(a.config, a.layers)
+    V, n, res = hp["n_vocab"], a.pos1 - a.pos0, {}
+
+    class SP(ctypes.Structure):
+        _fields_ = [("seed", ctypes.c_int32), ("top_k", ctypes.c_int32), ("repeat_last_n", ctypes.c_int32),
+                    ("top_p", ctypes.c_float), ("temp", ctypes.c_float), ("repeat_penalty", ctypes.c_float)]
+
+    for mode, step in (("exact", L.vsim_model_decode_batch), ("fast", L.vsim_model_decode_batch_fast)):
+        res[mode] = {}
+        for B in bs:
+            seqs, lg, runs = np.arange(B, dtype=np.int32), np.zeros((B, V), np.float32), []
+            for r in range(a.repeats):
+                sm = []
+                for b in range(B):
+                    p, s = SP(1 + b, 20, 64, 0.95, 0.85, 1.3), vp()
+                    ck(L.vsim_sampler_create(ctypes.byref(p), ctypes.byref(s)), "sampler_create")
+                    sm.append(s)
+                tok, t0, t = np.arange(3, 3 + B, dtype=np.int32), 0.0, ctypes.c_int32()
+                for p in range(a.pos1):
+                    if p == a.pos0:
+                        t0 = time.perf_counter()
+                    npst = np.full(B, p, np.int32)
+                    ck(step(h, B, seqs.ctypes.data, npst.ctypes.data, tok.ctypes.data, lg.ctypes.data, None), "decode_batch")
+                    for b in range(B):
+                        ck(L.vsim_sampler_sample_host(sm[b], lg[b].ctypes.data, V, ctypes.byref(t)), "sample_host")
+                        tok[b] = t.value
+                runs.append(B * n / (time.perf_counter() - t0))
+                for s in sm:
+                    L.vsim_sampler_free(s)
+            res[mode][B] = {"tok_s": statistics.median(runs), "runs": runs}
+    L.vsim_model_free(h)
+    print(json.dumps(res))
+
+
+def timed_sample_steps(dm, hip, B, pos0, pos1, fast):
+    """timed_steps through decode_batch_sample, a fresh sampler per row."""
+    sm = [hip.Sampler(seed=1 + b, **SAMPLE_PARAMS) for b in range(B)]
+    seqs, tok, t0 = list(range(B)), [3 + b for b in range(B)], 0.0
+    for p in range(pos1):
+        if p == pos0:
+            t0 = time.perf_counter()
+        tok = [int(t) for t in dm.decode_batch_sample(seqs, [p] * B, tok, sm, fast=fast)]
+    dt = time.perf_counter() - t0
+    assert all(s.stats() == {"device": pos1, "host": 0} for s in sm)
+    return dt
+
+
+def main_sample(a):
+    """--sample: the sampled step against the greedy step and the parent's logits-out + host sampler."""
+    from vsim_amd import hip
+    import torch
+    arch_s, hp = hparams(a.config, a.layers)
+    bs = [int(b) for b in a.bs.split(",")]
+    dm = hip.Model.create(ARCH[arch_s], hp, n_ctx=a.n_ctx)
+    dm.randomize(seed=1, std=0.02)
+    dm.set_mode(hip.MODE_EXACT)  # (decode_batch_fast and the fast sampled step serve a model in either mode)
+    dm.seq_reserve(max(bs))
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    box = f"{socket.gethostname()} {torch.cuda.get_device_properties(0).gcnArchName}"
+    n = a.pos1 - a.pos0
+    say(f"# batch_bench --sample: {a.config} shape, {hp['n_layer']} layers, random weights (std 0.02), n_ctx {a.n_ctx}; "
+        f"box {box}; tree at {a.tree}")
+    say(f"# aggregate tok/s over positions {a.pos0}..{a.pos1 - 1} ({n} steps, positions 0..{a.pos0 - 1} discarded as warm-up), "
+        f"wall clock round calls that end in a stream synchronize; median of {a.repeats} repeats, sampled and greedy "
+        f"alternating inside each repeat; samplers: {SAMPLE_PARAMS}, seed 1 + row")
+    res = {}
+    for mode, fast in (("exact", False), ("fast", True)):
+        res[mode] = {}
+        for B in bs:
+            runs = {"sampled": [], "greedy": []}
+            for r in range(a.repeats):
+                for v in (("sampled", "greedy") if r % 2 == 0 else ("greedy", "sampled")):
+                    dt = timed_sample_steps(dm, hip, B, a.pos0, a.pos1, fast) if v == "sampled" else \
+                        timed_steps(dm, B, a.pos0, a.pos1, fast=fast)
+                    runs[v].append(B * n / dt)
+            res[mode][B] = {v: statistics.median(x) for v, x in runs.items()}
+            r_ = res[mode][B]
+            say(f"{mode:5s} B {B:2d}: decode_batch_sample {r_['sampled']:9.1f} tok/s   greedy step {r_['greedy']:9.1f} tok/s   "
+                f"sampled/greedy {r_['sampled'] / r_['greedy']:5.3f}   step {1e3 * B / r_['sampled']:7.3f} ms against "
+                f"{1e3 * B / r_['greedy']:7.3f} ms   (runs {' '.join(f'{v:.0f}' for v in runs['sampled'])} | "
+                f"{' '.join(f'{v:.0f}' for v in runs['greedy'])})")
+    dm.close()
+    lib = a.baseline_lib or hip.LIB_PATH
+    who = "parent commit" if a.baseline_lib else "this library"
+    base = run_baseline(a, lib, "sample")
+    ok = True
+    for mode in ("exact", "fast"):
+        for B in bs:
+            b_ = base[mode][str(B)]
+            ratio = res[mode][B]["sampled"] / b_["tok_s"]
+            if B >= 4 and ratio <= 1.0:
+                ok = False
+            say(f"{mode:5s} B {B:2d}: logits out + sample_host per row, {who}: {b_['tok_s']:9.1f} tok/s (step "
+                f"{1e3 * B / b_['tok_s']:7.3f} ms)   decode_batch_sample / that {ratio:5.2f}   "
+                f"(runs {' '.join(f'{x:.0f}' for x in b_['runs'])})")
+    for mode in ("exact", "fast"):
+        if 32 in res[mode]:
+            r_, b_ = res[mode][32], base[mode]["32"]
+            say(f"{mode} B = 32: sampling costs {1e3 * 32 / r_['sampled'] - 1e3 * 32 / r_['greedy']:+.3f} ms per step over the "
+                f"greedy step; the host sampler path costs {1e3 * 32 / b_['tok_s'] - 1e3 * 32 / r_['greedy']:+.3f} ms over it")
+    say(f"decode_batch_sample faster than logits out + sample_host at every B >= 4, both modes: {'yes' if ok else 'NO'}")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def run_baseline(a, lib, kind="generate", mode="exact"):
@@ -221,6 +358,7 @@ def main_fast(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="exact", choices=["exact", "fast"])
+    ap.add_argument("--sample", action="store_true", help="the sampled step, both modes (see the module text)")
     ap.add_argument("--child-kind", default="generate", help=argparse.SUPPRESS)
     ap.add_argument("--child-mode", default="exact", help=argparse.SUPPRESS)
     ap.add_argument("--config", default="gpt-j-6B")
@@ -237,9 +375,11 @@ def main():
     ap.add_argument("--baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--lib", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
-    a.bs = a.bs or ("1,2,4,8,12,16,24,32" if a.mode == "fast" else "1,2,4,8,16,32")
+    a.bs = a.bs or ("1,4,8,16,32" if a.sample else "1,2,4,8,12,16,24,32" if a.mode == "fast" else "1,2,4,8,16,32")
     if a.baseline_child:
         return baseline_child(a)
+    if a.sample:
+        return main_sample(a)
     if a.mode == "fast":
         return main_fast(a)
 

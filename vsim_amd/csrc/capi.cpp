@@ -224,6 +224,35 @@ int vsim_op_topk(const float *x, int n, const int32_t *win, int nw, double scale
   }
   return launch_topk(x, n, nullptr, win, nw, scale, repeat_penalty, k, val, id, ws, (hipStream_t)stream);
 }
+static_assert(sizeof(vsim_topk_params) == sizeof(TopkParams) && offsetof(vsim_topk_params, scale) == offsetof(TopkParams, scale) &&
+                  offsetof(vsim_topk_params, penalty) == offsetof(TopkParams, penalty) &&
+                  offsetof(vsim_topk_params, k) == offsetof(TopkParams, k) &&
+                  offsetof(vsim_topk_params, nw) == offsetof(TopkParams, nw) &&
+                  offsetof(vsim_topk_params, win) == offsetof(TopkParams, win),
+              "vsim_topk_params is TopkParams");
+static_assert(sizeof(vsim_topk_out) == sizeof(TopkOut) && offsetof(vsim_topk_out, val) == offsetof(TopkOut, val) &&
+                  offsetof(vsim_topk_out, id) == offsetof(TopkOut, id),
+              "vsim_topk_out is TopkOut");
+int vsim_op_topk_rows(const float *x, int ldx, int n, int B, const vsim_topk_params *pb, vsim_topk_out *out,
+                      void *stream) {
+  // VSIM_BATCH_MAX row blocks per (device, stream), kept, as vsim_op_topk's: every row's counter is left zero
+  static std::mutex mu;
+  static std::map<std::pair<int, void *>, void *> wss;
+  int dev = 0;
+  VSIM_HIP(hipGetDevice(&dev));
+  void *ws = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    void *&w = wss[{dev, stream}];
+    if (!w) {
+      VSIM_HIP(hipMalloc(&w, VSIM_BATCH_MAX * TOPK_WS_BYTES));
+      VSIM_HIP(hipMemset(w, 0, VSIM_BATCH_MAX * TOPK_WS_BYTES));
+    }
+    ws = w;
+  }
+  return launch_topk_rows(x, ldx, n, B, (const TopkParams *)pb, (TopkOut *)out, ws, (hipStream_t)stream);
+}
+int vsim_topk_rows_set_wg(int per_row) { return topk_rows_set_wg(per_row); }
 int vsim_op_logprob(const float *x, int V, int R, const int32_t *target, double *logprob, int32_t *argmax, void *stream) {
   return launch_score_rows(x, V, R, target, logprob, argmax, (hipStream_t)stream);
 }

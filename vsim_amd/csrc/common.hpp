@@ -347,6 +347,11 @@ constexpr int TOPK_MAX_WG = 64;
 constexpr size_t TOPK_WS_BYTES = 256 + (size_t)TOPK_MAX_WG * 64 * (sizeof(unsigned long long) + sizeof(uint32_t));
 int launch_topk(const float *x, int n, const TopkParams *pb, const int32_t *win, int nw, double scale, double penalty,
                 int k, double *val, int32_t *id, void *ws, hipStream_t s);
+// The same for B rows x[B][ldx] in one launch (k_sample_topk_rows, vsim_op_topk_rows): row b with
+// the device block pb[b] into out[b], each bit for bit launch_topk's of that row alone.  ws:
+// B * TOPK_WS_BYTES, the first word of every row's block zero (left zero).
+int launch_topk_rows(const float *x, int ldx, int n, int B, const TopkParams *pb, TopkOut *out, void *ws, hipStream_t s);
+int topk_rows_set_wg(int per_row);  // vsim_topk_rows_set_wg; returns the old setting
 // Per-row log-probability and greedy id of R logit rows x[R][V] (score.hip, vsim_op_logprob):
 // one workgroup per row, a fixed summation order per row; target / logprob / argmax may be null
 // (not both outputs)

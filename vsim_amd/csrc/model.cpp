@@ -180,6 +180,12 @@ struct vsim_model {
   float *score_x = nullptr;
   int32_t *score_tgt = nullptr, *score_tgt_host = nullptr;
   void *score_out = nullptr, *score_out_host = nullptr;
+  // the sampled batched step (vsim_model_decode_batch_sample), allocated with them: a parameter
+  // block per row (pinned, device), the rows' candidates (device, pinned) and k_sample_topk_rows'
+  // workspace (every row's counter zero between launches)
+  TopkParams *bs_par_host = nullptr, *bs_par_dev = nullptr;
+  TopkOut *bs_out_dev = nullptr, *bs_out_host = nullptr;
+  void *bs_ws = nullptr;
 
   // graph executor's fast path (graph.cpp): weights and KV cache borrowed from its device
   // mirrors (not freed here), the KQV key grouping of the caller's thread count and the
@@ -303,6 +309,12 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->score_tgt_host, sn * sizeof(int32_t), S_PINNED | S_SCORE);
   add(&m->score_out, sn * so, S_SCORE);
   add(&m->score_out_host, sn * so, S_PINNED | S_SCORE);
+  const size_t bs = m->score_rows ? VSIM_BATCH_MAX : 0;
+  add(&m->bs_par_host, bs * sizeof(TopkParams), S_PINNED | S_SCORE);
+  add(&m->bs_par_dev, bs * sizeof(TopkParams), S_SCORE);
+  add(&m->bs_out_dev, bs * sizeof(TopkOut), S_SCORE);
+  add(&m->bs_out_host, bs * sizeof(TopkOut), S_PINNED | S_SCORE);
+  add(&m->bs_ws, bs * TOPK_WS_BYTES, S_ZERO | S_SCORE);
   return t;
 }
 
@@ -362,11 +374,11 @@ int ensure_score_scratch(vsim_model *m, int rows) {
   for (const ScratchBuf &b : scratch_table(m, m->n_max)) {
     if (!(b.flags & S_SCORE) || !b.bytes) continue;
     const hipError_t e = b.flags & S_PINNED ? hipHostMalloc(b.p, b.bytes, hipHostMallocDefault) : hipMalloc(b.p, b.bytes);
-    if (e != hipSuccess) {
-      *b.p = nullptr;
+    if (e != hipSuccess || ((b.flags & S_ZERO) && hipMemset(*b.p, 0, b.bytes) != hipSuccess)) {
+      if (e != hipSuccess) *b.p = nullptr;
       release();
       m->score_rows = 0;
-      return hip_fail(e, "score scratch");
+      return hip_fail(e != hipSuccess ? e : hipErrorUnknown, "score scratch");
     }
   }
   return VSIM_OK;
@@ -2283,8 +2295,9 @@ int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *token
 namespace {
 // One batched decode step with the products in `mode` (vsim_model_decode_batch: exact, on a model in
 // exact mode; vsim_model_decode_batch_fast: fast, whatever the model's mode)
+// -- or, with samplers, the sampled step (vsim_model_decode_batch_sample): next[b] drawn by samplers[b]
 int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
-                      const int32_t *tokens, float *logits, int32_t *next) {
+                      const int32_t *tokens, float *logits, int32_t *next, vsim_sampler *const *samplers = nullptr) {
   if (!m || !seq || !n_past || !tokens) { set_error("decode_batch: null argument"); return VSIM_EINVAL; }
   if (!m->first || !m->last) { set_error("decode_batch: needs a whole model"); return VSIM_EINVAL; }
   if (mode == VSIM_MODE_EXACT && m->mode != VSIM_MODE_EXACT) {
@@ -2302,6 +2315,19 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
     if (seq[b] < 64) used |= (uint64_t)1 << seq[b];
     if (n_past[b] < 0 || n_past[b] >= m->n_ctx) { set_error("decode_batch: n_past outside [0, n_ctx)"); return VSIM_EINVAL; }
     if (tokens[b] < 0 || tokens[b] >= V) { set_error("decode_batch: token id out of range"); return VSIM_EINVAL; }
+  }
+  // the sampled step: which rows' candidates the device makes (the others: sample_host on the row's logits)
+  bool on_dev[VSIM_BATCH_MAX] = {};
+  bool any_dev = false;
+  for (int b = 0; samplers && b < B; ++b) {
+    const vsim_sampler *sm = samplers[b];
+    if (!sm) { set_error("decode_batch_sample: null sampler"); return VSIM_EINVAL; }
+    for (int a = 0; a < b; ++a)
+      if (samplers[a] == sm) { set_error("decode_batch_sample: a sampler is named twice"); return VSIM_EINVAL; }
+    if (sm->top_k < 1) { set_error("decode_batch_sample: top_k < 1"); return VSIM_EINVAL; }
+    on_dev[b] = !(sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX ||
+                  !(sm->temp > 0.0) || !(sm->repeat_penalty > 0.0));
+    any_dev |= on_dev[b];
   }
   m->st_npast = -1;  // as an eval: a stage step needs a new stage_begin
   VSIM_HIP(hipSetDevice(m->device));
@@ -2321,6 +2347,39 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
   RC(enqueue_prompt(m, 0, tokens, B, nullptr, nk, "decode_batch", nullptr, nullptr, m->bw_dev, rows_gemm, mode));
   RC(run_head(m, m->inpL, B, m->score_x, "lm_head (batch)", nk, rows_gemm, mode));
   int32_t *am_dev = (int32_t *)m->score_out;
+  if (samplers) {
+    // the rows' parameter blocks (only the B in use travel), one launch for all rows, the B lists back;
+    // a host-path row's block asks for one candidate of an empty window, which nobody reads
+    for (int b = 0; b < B; ++b) {
+      TopkParams *pb = m->bs_par_host + b;
+      const vsim_sampler *sm = samplers[b];
+      pb->scale = on_dev[b] ? 1.0 / sm->temp : 1.0;
+      pb->penalty = on_dev[b] ? sm->repeat_penalty : 1.0;
+      pb->k = on_dev[b] ? sm->top_k : 1;
+      pb->nw = on_dev[b] ? (int32_t)sm->win.size() : 0;
+      if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
+    }
+    if (any_dev) {
+      VSIM_HIP(hipMemcpyAsync(m->bs_par_dev, m->bs_par_host, sizeof(TopkParams) * B, hipMemcpyHostToDevice, s));
+      LAUNCH(m, nk, launch_topk_rows(m->score_x, V, V, B, m->bs_par_dev, m->bs_out_dev, m->bs_ws, s),
+             "k_sample_topk_rows", (double)B * V * sizeof(float));
+      VSIM_HIP(hipMemcpyAsync(m->bs_out_host, m->bs_out_dev, sizeof(TopkOut) * B, hipMemcpyDeviceToHost, s));
+    }
+    std::vector<std::vector<float>> host_rows((size_t)B);
+    for (int b = 0; b < B; ++b) {
+      if (on_dev[b]) continue;
+      host_rows[b].resize((size_t)V);
+      VSIM_HIP(hipMemcpyAsync(host_rows[b].data(), m->score_x + (size_t)b * V, sizeof(float) * V, hipMemcpyDeviceToHost, s));
+    }
+    RC(finish_call(m, nk));
+    for (int b = 0; b < B; ++b) {
+      if (on_dev[b])
+        RC(vsim_sampler_pick(samplers[b], m->bs_out_host[b].val, m->bs_out_host[b].id, samplers[b]->top_k, &next[b]));
+      else
+        RC(vsim_sampler_sample_host(samplers[b], host_rows[b].data(), V, &next[b]));
+    }
+    return VSIM_OK;
+  }
   if (next) {
     LAUNCH(m, nk, launch_score_rows(m->score_x, V, B, nullptr, nullptr, am_dev, s), "k_score_rows",
            (double)B * V * sizeof(float));
@@ -2341,6 +2400,35 @@ int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int3
 int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
                                  const int32_t *tokens, float *logits, int32_t *next) {
   return decode_batch_impl(m, VSIM_MODE_FAST, B, seq, n_past, tokens, logits, next);
+}
+
+int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
+                                   const int32_t *tokens, vsim_sampler *const *samplers, int32_t *next) {
+  if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST) {
+    set_error("decode_batch_sample: mode must be VSIM_MODE_EXACT or VSIM_MODE_FAST");
+    return VSIM_EINVAL;
+  }
+  if (!samplers || !next) { set_error("decode_batch_sample: null argument"); return VSIM_EINVAL; }
+  return decode_batch_impl(m, mode, B, seq, n_past, tokens, nullptr, next, samplers);
+}
+
+int vsim_model_seq_copy(vsim_model *m, int dst, int src, int n_tokens) {
+  if (!m) { set_error("seq_copy: null model"); return VSIM_EINVAL; }
+  if (m->borrowed || !m->first || !m->last) {
+    set_error("seq_copy: needs a whole model that owns its KV cache");
+    return VSIM_EINVAL;
+  }
+  const int nslot = 1 + (int)m->kslot.size();
+  if (dst < 0 || dst >= nslot || src < 0 || src >= nslot) { set_error("seq_copy: slot outside the reserve (seq_reserve)"); return VSIM_EINVAL; }
+  if (dst == src) { set_error("seq_copy: dst == src"); return VSIM_EINVAL; }
+  if (n_tokens < 1 || n_tokens > m->n_ctx) { set_error("seq_copy: n_tokens must be in 1..n_ctx"); return VSIM_EINVAL; }
+  VSIM_HIP(hipSetDevice(m->device));
+  // a slot is [layers][n_ctx][E]: the first n_tokens rows of every layer, one strided copy per cache
+  const size_t pitch = (size_t)m->n_ctx * E_(m) * sizeof(float), width = (size_t)n_tokens * E_(m) * sizeof(float);
+  const size_t layers = (size_t)(m->l1 - m->l0);
+  VSIM_HIP(hipMemcpy2DAsync(slot_k(m, dst), pitch, slot_k(m, src), pitch, width, layers, hipMemcpyDeviceToDevice, m->stream));
+  VSIM_HIP(hipMemcpy2DAsync(slot_v(m, dst), pitch, slot_v(m, src), pitch, width, layers, hipMemcpyDeviceToDevice, m->stream));
+  return VSIM_OK;
 }
 
 int vsim_score_set_chunk_rows(int rows) { return g_score_chunk_rows.exchange(rows > 0 ? rows : 0); }

@@ -29,6 +29,7 @@
 // window once per span: one bit test per logit instead of nw compares.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <string>
 
 #include "common.hpp"
@@ -36,6 +37,7 @@
 namespace vsim {
 
 constexpr int TK_T = 1024, TK_WAVES = TK_T / 64, TK_SPAN = 8192;
+constexpr int TOPK_ROWS_WG = 256;  // workgroups of all rows together (one per CU) before a row gets fewer
 constexpr uint32_t TK_ID = 0x7FFFFFFFu, TK_INWIN = 0x80000000u;  // id bits; "penalised" flag
 
 __device__ __forceinline__ unsigned long long tk_key(double c) {
@@ -153,36 +155,35 @@ __device__ __forceinline__ void tk_merge_waves(unsigned long long &LK, uint32_t 
   }
 }
 
-__global__ void __launch_bounds__(TK_T)
-    k_sample_topk(const float *__restrict__ x, int n, const TopkParams *__restrict__ pb, const int32_t *win, int nw,
-                  double scale, double penalty, int k, double *__restrict__ val, int32_t *__restrict__ id,
-                  unsigned char *ws) {
+// One row's candidates, by the G workgroups the row is split over (this one is the g-th): the
+// body of k_sample_topk (one row, G = the grid) and of k_sample_topk_rows (G workgroups per row,
+// one ws block per row).  The result is the best kk of the row under the total order above, so it
+// depends neither on G nor on which workgroup walks which span.  ws: the row's TOPK_WS_BYTES, its
+// first word zero (left zero).  Called by the whole workgroup.
+__device__ __forceinline__ void tk_row(const float *__restrict__ x, int n, const int32_t *win, int nw, double scale,
+                                       double penalty, int k, double *__restrict__ val, int32_t *__restrict__ id,
+                                       unsigned char *ws, int g, int G) {
   __shared__ uint32_t bm[TK_SPAN / 32];
   __shared__ unsigned long long sK[TK_T];
   __shared__ uint32_t sI[TK_T];
   __shared__ int s_last;
-  if (pb) {
-    win = pb->win;
-    nw = pb->nw;
-    scale = pb->scale;
-    penalty = pb->penalty;
-    k = pb->k;
-  }
   // (the callers checked the limits; a block holding anything else must still stay in bounds)
   const int kk = k < 1 ? 1 : k > VSIM_TOPK_MAX ? VSIM_TOPK_MAX : k;
   nw = nw < 0 ? 0 : nw > VSIM_WINDOW_MAX ? VSIM_WINDOW_MAX : nw;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, G = gridDim.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   unsigned *cnt = (unsigned *)ws;
   unsigned long long *wK = (unsigned long long *)(ws + 256);
   uint32_t *wI = (uint32_t *)(ws + 256 + (size_t)TOPK_MAX_WG * 64 * sizeof(unsigned long long));
 
-  // spans of S consecutive ids, dealt round-robin (one per workgroup up to n = 64 * 8192)
+  // spans of S <= 8192 consecutive ids, dealt round-robin: one per workgroup while the
+  // workgroup's share fits a span, else the share in equal spans
   const long long per = (((long long)n + G - 1) / G + 255) & ~255ll;
-  const int S = per > TK_SPAN ? TK_SPAN : (int)per;
+  const long long nsp = (per + TK_SPAN - 1) / TK_SPAN;
+  const int S = (int)(((per + nsp - 1) / nsp + 255) & ~255ll);
   const long long nspan = ((long long)n + S - 1) / S;
   unsigned long long LK = 0;
   uint32_t LI = TK_ID;
-  for (long long c = blockIdx.x; c < nspan; c += G) {
+  for (long long c = g; c < nspan; c += G) {
     const long long base = c * S;
     const int len = n - base < S ? (int)(n - base) : S;
     if (tid < S / 32) bm[tid] = 0;
@@ -211,11 +212,11 @@ __global__ void __launch_bounds__(TK_T)
   if (wave == 0) {
     // The hand-off is the first row of MI355X_MICROARCH.md's sc1 hand-off table, as k_argmax's: the
     // one storing wave writes its list with device-coherent (sc1) stores and drains them
-    // (vmcnt(0)); then one lane adds to the unsharded counter.  The workgroup whose add returns
-    // G - 1 reads the lists with sc1 loads, the adding wave after its add returned, the other
-    // waves behind the workgroup barrier below.  Nobody waits for anybody.
-    __hip_atomic_store(&wK[blockIdx.x * 64 + lane], LK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&wI[blockIdx.x * 64 + lane], LI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (vmcnt(0)); then one lane adds to the row's unsharded counter.  The workgroup whose add
+    // returns G - 1 reads the row's lists with sc1 loads, the adding wave after its add returned,
+    // the other waves behind the workgroup barrier below.  Nobody waits for anybody.
+    __hip_atomic_store(&wK[g * 64 + lane], LK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&wI[g * 64 + lane], LI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0)
       s_last = __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)G - 1;
@@ -223,11 +224,11 @@ __global__ void __launch_bounds__(TK_T)
   __syncthreads();
   if (!s_last) return;
 
-  // last workgroup: wave w merges lists w, w + 16, ..; then the waves as above
+  // the row's last workgroup: wave w merges lists w, w + 16, ..; then the waves as above
   LK = 0;
   LI = TK_ID;
-  for (int g = wave; g < G; g += TK_WAVES) {
-    const int r = g * 64 + 63 - lane;  // the list worst first
+  for (int q = wave; q < G; q += TK_WAVES) {
+    const int r = q * 64 + 63 - lane;  // the list worst first
     const unsigned long long ck = __hip_atomic_load(&wK[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t ci = __hip_atomic_load(&wI[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     tk_merge_sorted(LK, LI, ck, ci);
@@ -241,6 +242,32 @@ __global__ void __launch_bounds__(TK_T)
     id[lane] = i;
   }
   if (lane == 0) __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ void __launch_bounds__(TK_T)
+    k_sample_topk(const float *__restrict__ x, int n, const TopkParams *__restrict__ pb, const int32_t *win, int nw,
+                  double scale, double penalty, int k, double *__restrict__ val, int32_t *__restrict__ id,
+                  unsigned char *ws) {
+  if (pb) {
+    win = pb->win;
+    nw = pb->nw;
+    scale = pb->scale;
+    penalty = pb->penalty;
+    k = pb->k;
+  }
+  tk_row(x, n, win, nw, scale, penalty, k, val, id, ws, blockIdx.x, gridDim.x);
+}
+
+// B rows in one launch: grid (G, B), workgroup (g, b) is the g-th of row b's G.  Row b reads
+// x + b * ldx and pb[b], writes out[b] and hands off through its own block of ws; the rows share
+// nothing, so a row's result is k_sample_topk's of that row alone.
+__global__ void __launch_bounds__(TK_T)
+    k_sample_topk_rows(const float *__restrict__ x, long long ldx, int n, const TopkParams *__restrict__ pb,
+                       TopkOut *__restrict__ out, unsigned char *ws) {
+  const int b = blockIdx.y;
+  const TopkParams *p = pb + b;
+  tk_row(x + (size_t)b * ldx, n, p->win, p->nw, p->scale, p->penalty, p->k, out[b].val, out[b].id,
+         ws + (size_t)b * TOPK_WS_BYTES, blockIdx.x, gridDim.x);
 }
 
 int launch_topk(const float *x, int n, const TopkParams *pb, const int32_t *win, int nw, double scale, double penalty,
@@ -260,6 +287,35 @@ int launch_topk(const float *x, int n, const TopkParams *pb, const int32_t *win,
   int g = (n + 1023) / 1024;
   g = g < 1 ? 1 : g > TOPK_MAX_WG ? TOPK_MAX_WG : g;
   hipLaunchKernelGGL(k_sample_topk, dim3(g), dim3(TK_T), 0, s, x, n, pb, win, nw, scale, penalty, k, val, id,
+                     (unsigned char *)ws);
+  VSIM_HIP(hipGetLastError());
+  return VSIM_OK;
+}
+
+static std::atomic<int> g_rows_wg{0};
+int topk_rows_set_wg(int per_row) {
+  return g_rows_wg.exchange(per_row < 0 ? 0 : per_row > TOPK_MAX_WG ? TOPK_MAX_WG : per_row);
+}
+
+int launch_topk_rows(const float *x, int ldx, int n, int B, const TopkParams *pb, TopkOut *out, void *ws, hipStream_t s) {
+  if (!x || !pb || !out || !ws || n < 1 || ldx < n || B < 1 || B > VSIM_BATCH_MAX) {
+    set_error("topk_rows: bad argument (1 <= B <= " + std::to_string(VSIM_BATCH_MAX) + ", 1 <= n <= ldx)");
+    return VSIM_EINVAL;
+  }
+  // Workgroups per row: k_sample_topk's (1024 ids each, at most 64) while all rows' together are
+  // at most one per CU; beyond that the rows supply the parallelism and a workgroup walks a longer
+  // share, which costs it little (after its first batches few candidates pass the k-th entry)
+  // while every workgroup less is a list less to hand off and merge.  Measured at 32 rows
+  // (profiles/batch_sample_bench.txt): 8 per row beat 16, 32 and 64 at n = 50,400 and 250,880.
+  // topk_rows_set_wg overrides (same results: tk_row).
+  int g = (n + 1023) / 1024;
+  g = g < 1 ? 1 : g > TOPK_MAX_WG ? TOPK_MAX_WG : g;
+  const int fixed = g_rows_wg.load();
+  if (fixed > 0)
+    g = g < fixed ? g : fixed;
+  else if (B * g > TOPK_ROWS_WG)
+    g = TOPK_ROWS_WG / B;  // >= 8
+  hipLaunchKernelGGL(k_sample_topk_rows, dim3(g, B), dim3(TK_T), 0, s, x, (long long)ldx, n, pb, out,
                      (unsigned char *)ws);
   VSIM_HIP(hipGetLastError());
   return VSIM_OK;

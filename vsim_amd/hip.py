@@ -54,6 +54,7 @@ EXPORTS = [
     "vsim_op_q4_gemm_fast_rows", "vsim_batch_set_fast_gemm", "vsim_model_decode_batch_fast",
     "vsim_op_attn_prefill_layout", "vsim_op_attn_prefill_scratch", "vsim_op_gemm_q4_256_h16",
     "vsim_op_gemm_q4_256_pair_h16",
+    "vsim_op_topk_rows", "vsim_topk_rows_set_wg", "vsim_model_decode_batch_sample", "vsim_model_seq_copy",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -111,6 +112,22 @@ def ggml_f32(buf, ne, nb=None, typ=GGML_TYPE_F32):
 class SampleParams(ctypes.Structure):
     _fields_ = [("seed", ctypes.c_int32), ("top_k", ctypes.c_int32), ("repeat_last_n", ctypes.c_int32),
                 ("top_p", ctypes.c_float), ("temp", ctypes.c_float), ("repeat_penalty", ctypes.c_float)]
+
+
+class TopkParams(ctypes.Structure):
+    """vsim_topk_params (include/vsim_hip.h): one row's block for topk_rows, 4,120 bytes."""
+    _fields_ = [("scale", ctypes.c_double), ("penalty", ctypes.c_double), ("k", ctypes.c_int32),
+                ("nw", ctypes.c_int32), ("win", ctypes.c_int32 * WINDOW_MAX)]
+
+
+class TopkOut(ctypes.Structure):
+    """vsim_topk_out: one row's candidates, 768 bytes."""
+    _fields_ = [("val", ctypes.c_double * TOPK_MAX), ("id", ctypes.c_int32 * TOPK_MAX)]
+
+
+TOPK_PARAMS_DTYPE = np.dtype([("scale", "<f8"), ("penalty", "<f8"), ("k", "<i4"), ("nw", "<i4"),
+                              ("win", "<i4", (WINDOW_MAX,))])
+TOPK_OUT_DTYPE = np.dtype([("val", "<f8", (TOPK_MAX,)), ("id", "<i4", (TOPK_MAX,))])
 
 
 # the fast decode step's launches (vsim_op_fast_* in include/vsim_hip.h)
@@ -278,6 +295,10 @@ def lib():
     L.vsim_op_q4_gemm_fast_rows.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.vsim_batch_set_fast_gemm.argtypes = [ci]
     L.vsim_model_decode_batch_fast.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.vsim_op_topk_rows.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+    L.vsim_topk_rows_set_wg.argtypes = [ci]
+    L.vsim_model_decode_batch_sample.argtypes = [vp, ci, ci, vp, vp, vp, ctypes.POINTER(vp), vp]
+    L.vsim_model_seq_copy.argtypes = [vp, ci, ci, ci]
     _lib = L
     return L
 
@@ -379,6 +400,22 @@ def topk(x, n, win, scale, repeat_penalty, k, val, ids, stream=None):
     nw = 0 if win is None else int(win.numel() if hasattr(win, "numel") else win.size)
     check(lib().vsim_op_topk(addr(x), n, addr(win) if nw else None, nw, float(scale), float(repeat_penalty), k,
                              addr(val), addr(ids), stream), "topk")
+
+
+def topk_rows(x, ldx, n, B, params, out, stream=None):
+    """vsim_op_topk_rows on device buffers (torch tensors or raw addresses): x float32 [B][ldx] (an
+    int address allows any 4-byte alignment), params B TopkParams blocks (a uint8 tensor holding
+    TOPK_PARAMS_DTYPE records), out B TopkOut blocks (TOPK_OUT_DTYPE).  Row b's out.val[0:k_b],
+    out.id[0:k_b] are topk()'s of that row alone.  Enqueued on `stream`, not synchronized."""
+    def addr(t):
+        return t if isinstance(t, int) or t is None else ptr(t)
+    check(lib().vsim_op_topk_rows(addr(x), int(ldx), int(n), int(B), addr(params), addr(out), stream), "topk_rows")
+
+
+def topk_rows_set_wg(per_row) -> int:
+    """Workgroups per row of topk_rows (0: the default rule); same results whatever the setting.
+    Returns the previous setting."""
+    return int(lib().vsim_topk_rows_set_wg(int(per_row)))
 
 
 def logprob(x, V, R, target, logprob, argmax, stream=None):
@@ -581,6 +618,28 @@ class Model:
         nxt = np.zeros(max(B, 1), np.int32)
         check(fn(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)), who)
         return lg, nxt[:B]
+
+    def decode_batch_sample(self, seqs, n_past, tokens, samplers, fast=False):
+        """One sampled decode step for len(seqs) sequences: decode_batch (or decode_batch_fast), then
+        row b's token drawn by samplers[b] -- the candidate stage of all rows in one launch on the
+        device, the draw on the host.  Every row's token and sampler state are those of eval_sample
+        on that sequence alone.  Returns next int32 [B]."""
+        sq = np.ascontiguousarray(seqs, np.int32)
+        npst = np.ascontiguousarray(n_past, np.int32)
+        tok = np.ascontiguousarray(tokens, np.int32)
+        samplers = list(samplers)
+        if not (sq.size == npst.size == tok.size == len(samplers)):
+            raise ValueError("decode_batch_sample: one slot, position, token and sampler per row")
+        B = int(sq.size)
+        hs = (ctypes.c_void_p * max(B, 1))(*[None if sm is None else sm.h for sm in samplers])
+        nxt = np.zeros(max(B, 1), np.int32)
+        check(lib().vsim_model_decode_batch_sample(self.h, MODE_FAST if fast else MODE_EXACT, B, ptr(sq), ptr(npst),
+                                                   ptr(tok), hs, ptr(nxt)), "decode_batch_sample")
+        return nxt[:B]
+
+    def seq_copy(self, dst, src, n_tokens):
+        """Slot fork: the first n_tokens cache rows of slot src go to slot dst (on the model's stream)."""
+        check(lib().vsim_model_seq_copy(self.h, int(dst), int(src), int(n_tokens)), "seq_copy")
 
     def eval_argmax(self, n_past, token) -> int:
         """Greedy decode step: the next token (argmax of the logits, taken on the device)."""
