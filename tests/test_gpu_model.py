@@ -278,6 +278,90 @@ def test_prompt_kernel_counts(cfg, mode):
     assert tuple(got) == PROMPT_KERNELS[cfg][mode]
 
 
+# The batched decode steps whose launches are pinned: (call, B, product switch).  The switch is
+# batch_set_gemm for decode_batch and batch_set_fast_gemm for decode_batch_fast (0: the GEMV paths,
+# 2: the rows GEMM at every B); the B values stand on both sides of the default thresholds (12 and
+# 4 rows).  The sampled step runs with both switches at their default.
+BATCH_STEPS = [("decode_batch", 3, 0), ("decode_batch", 3, 2), ("decode_batch", 12, 0), ("decode_batch", 12, 2),
+               ("decode_batch_fast", 3, 0), ("decode_batch_fast", 3, 2), ("decode_batch_fast", 4, 0),
+               ("decode_batch_fast", 4, 2), ("decode_batch_sample", 3, 1)]
+
+
+def batch_launch_lists(cfg):
+    """{(call, B, switch): (kernels_per_eval, ((profile name, launches), ...))} of every BATCH_STEPS
+    step on a 2-layer model of `cfg` in exact mode after seq_reserve(16), all rows at position 0:
+    the count from an unprofiled step, the list from the same step with profiling on."""
+    arch_s, hp = mg.CONFIGS[cfg]
+    arch = {"gptj": hip.ARCH_GPTJ, "gptneox": hip.ARCH_GPTNEOX, "bloom": hip.ARCH_BLOOM}[arch_s]
+    m = hip.Model.create(arch, dict(n_vocab=hp.n_vocab, n_embd=hp.n_embd, n_head=hp.n_head, n_layer=hp.n_layer,
+                                    n_rot=hp.n_rot, use_parallel_residual=hp.use_parallel_residual), n_ctx=64)
+    m.randomize(11, 0.05)
+    m.set_mode(hip.MODE_EXACT)
+    m.seq_reserve(16)
+    out = {}
+    try:
+        for call, B, switch in BATCH_STEPS:
+            hip.batch_set_gemm(switch if call == "decode_batch" else 1)
+            hip.batch_set_fast_gemm(switch if call == "decode_batch_fast" else 1)
+            seqs, pos, tok = list(range(B)), [0] * B, [(7 * b + 3) % hp.n_vocab for b in range(B)]
+            if call == "decode_batch_sample":
+                sm = [hip.Sampler(seed=1 + b) for b in range(B)]
+                step = lambda: m.decode_batch_sample(seqs, pos, tok, sm)  # noqa: E731
+            else:
+                step = lambda: getattr(m, call)(seqs, pos, tok, want_logits=False)  # noqa: E731
+            step()
+            n = m.info()["kernels_per_eval"]
+            m.set_profile(True)
+            step()
+            assert m.info()["kernels_per_eval"] == n, (call, B, switch)
+            out[(call, B, switch)] = (n, tuple((k["name"], k["launches"]) for k in m.profile_kernels()))
+            m.set_profile(False)
+    finally:
+        hip.batch_set_gemm(1)
+        hip.batch_set_fast_gemm(1)
+        m.close()
+    return out
+
+
+# What batch_launch_lists gave on the commit before the executor's batch descriptor and product plan
+# (6ab4708), as literals: that refactor changed no launch.  The profile's lists are the same for the
+# three graphs; kernels_per_eval differs by their unprofiled launches (norms, quantizes, GELU, joins).
+# A fast step on per-row launches counts every row's launch of its 13 products (12 in the layers and
+# the lm_head): 26 more at B = 3, 39 more at B = 4.
+def _profile(products, last):
+    return ((products, 12), ("k_attn_decode_batch", 2), ("lm_head (batch)", 1), (last, 1))
+
+
+BATCH_PROFILE = {
+    ("decode_batch", 3, 0): _profile("gemv (prompt rows)", "k_score_rows"),
+    ("decode_batch", 3, 2): _profile("k_gemm_exact_rows (batch)", "k_score_rows"),
+    ("decode_batch", 12, 0): _profile("gemv (prompt rows)", "k_score_rows"),
+    ("decode_batch", 12, 2): _profile("k_gemm_exact_rows (batch)", "k_score_rows"),
+    ("decode_batch_fast", 3, 0): _profile("k_gemv_fast (batch, per row)", "k_score_rows"),
+    ("decode_batch_fast", 3, 2): _profile("k_gemm_fast_rows (batch)", "k_score_rows"),
+    ("decode_batch_fast", 4, 0): _profile("k_gemv_fast (batch, per row)", "k_score_rows"),
+    ("decode_batch_fast", 4, 2): _profile("k_gemm_fast_rows (batch)", "k_score_rows"),
+    ("decode_batch_sample", 3, 1): _profile("gemv (prompt rows)", "k_sample_topk_rows"),
+}
+# kernels_per_eval in BATCH_STEPS' order
+BATCH_KERNELS = {
+    "small-bloom": (36, 36, 36, 36, 62, 36, 75, 36, 36),
+    "small-gptj": (29, 29, 29, 29, 55, 29, 68, 29, 29),
+    "small-neox": (33, 33, 33, 33, 59, 33, 72, 33, 33),
+}
+
+
+@pytest.mark.parametrize("cfg", ["small-bloom", "small-gptj", "small-neox"])
+def test_batch_step_launch_lists(cfg):
+    """kernels_per_eval and the profile's (name, launches) list of the batched decode steps, exact,
+    fast and sampled, on either side of each product switch's threshold: exact integers and
+    strings, no margin."""
+    got = batch_launch_lists(cfg)
+    assert list(got) == BATCH_STEPS
+    for step, kernels in zip(BATCH_STEPS, BATCH_KERNELS[cfg]):
+        assert got[step] == (kernels, BATCH_PROFILE[step]), step
+
+
 @pytest.mark.parametrize("cfg", ["tiny-neox", "tiny-gptj"])
 def test_scratch_regrow_under_captured_graphs(cfg, tmp_path):
     """A prompt longer than the scratch (sized for 16 tokens) frees and regrows every scratch

@@ -68,6 +68,7 @@ int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n
   }
   return launch_gemm_fast_rows(w4_view(w, M, K), xq, n, bias, y, (hipStream_t)stream);
 }
+int vsim_batch_set_gemm(int enable) { return batch_set_gemm(enable); }
 int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
   if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->d <= 0 ||

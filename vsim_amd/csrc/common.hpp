@@ -13,6 +13,7 @@
 #include <string>
 
 #include "../../include/vsim_hip.h"
+#include "product_plan.hpp"
 
 namespace vsim {
 
@@ -307,6 +308,9 @@ int launch_quantize_w(const void *x, int src_type, int rows, int k, void *w, int
 int launch_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias,
                    float *y, int mode, hipStream_t s);
 int launch_gemv_batch(const GemvBatch &B, int mode, hipStream_t s);
+// n Q4 activation rows through the decode GEMV, `per` rows as the jobs of one launch
+int launch_gemv_rows(const W4 &W, const void *xq, const float *xd, int n, int per, const float *bias, float *y, int mode,
+                     hipStream_t s);
 // exact mode, N > 1 tokens: every (row, token) the reference's fp32 chain (gemm_exact.hip)
 int launch_gemm_exact(const W4 &W, const float *xd, int n, const float *bias, float *y, hipStream_t s);
 // exact mode, 1..VSIM_BATCH_MAX rows (the batched decode step): the same chains, each weight block
@@ -314,11 +318,9 @@ int launch_gemm_exact(const W4 &W, const float *xd, int n, const float *bias, fl
 int launch_gemm_exact_rows(const W4 &W, const float *xd, int n, const float *bias, float *y, hipStream_t s);
 // fast mode, 1..VSIM_BATCH_MAX rows (the fast batched decode step): k_gemv_fast's value of every
 // (weight row, activation row), bit for bit, each weight block fetched once per workgroup for all
-// rows (gemm_fast_rows.hip) -- or, by vsim_batch_set_fast_gemm, one k_gemv_fast launch per row.
-// xq: launch_q4_quantize's Q4 SoA rows
+// rows (gemm_fast_rows.hip) -- or, by vsim_batch_set_fast_gemm (product_plan), one k_gemv_fast launch
+// per row.  xq: launch_q4_quantize's Q4 SoA rows
 int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
-int batch_set_fast_gemm(int enable);   // vsim_batch_set_fast_gemm; returns the old setting
-bool batch_fast_gemm_rows(int n);      // true when launch_gemm_fast_rows runs n rows on k_gemm_fast_rows
 int launch_act_repack(const void *aos, void *xq, int n, int k, hipStream_t s);
 int launch_act_unpack(const void *xq, void *aos, int n, int k, hipStream_t s);
 int launch_q4_dequant(const void *xq, int rows, int k, float *y, hipStream_t s);
@@ -358,15 +360,12 @@ int topk_rows_set_wg(int per_row);  // vsim_topk_rows_set_wg; returns the old se
 int launch_score_rows(const float *x, int V, int R, const int32_t *target, double *logprob, int32_t *argmax,
                       hipStream_t s);
 int launch_gemm_q4_f16(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
-// fast-mode prompt batches (n >= GEMM_MIN_N): activation rows quantized (optionally after
-// bias + GELU) straight to the GEMM's fp16 operand x16 [n][K], and the GEMM on it
-constexpr int GEMM_MIN_N = 8;
+// fast-mode prompt batches (from GEMM_MIN_N rows on, product_plan.hpp): activation rows quantized
+// (optionally after bias + GELU) straight to the GEMM's fp16 operand x16 [n][K], and the GEMM on it
 int launch_act_quant_f16(const float *x, int K, int n, const float *bias, bool gelu, void *x16, hipStream_t s);
 int launch_gemm_f16x(const W4 &W, const void *x16, int n, const float *bias, float *y, hipStream_t s);
 // long prompts: fp16 weight images (launch_w4_expand_f16: [M][K], 2 bytes per weight) and the
 // 256 x 256-tile GEMM on them (K % 64 == 0), same operand values as launch_gemm_f16x
-constexpr int EXACT_GEMV_MAX_N = 32;  // exact prompt batches up to this many tokens run as batched decode GEMVs (ops_q4.hip)
-constexpr int G2_MIN_N = 256;
 int launch_w4_expand_f16(const W4 &W, void *out, hipStream_t s);
 // q16 non-null: y is not written; bias + GELU + Q4_0 quantize of the result into q16 ([n][M]
 // fp16 values d*(q-8), the next GEMM's operand, as launch_act_quant_f16(y, ..., gelu) makes)
@@ -392,7 +391,7 @@ struct G2Epi {
   int h16_ld = 0, h16_t = 0;
 };
 // the same GEMM straight from the W4T32 weight (dequantized to the same fp16 halves in LDS, no
-// image): what the model runs for N >= G2_MIN_N
+// image): what the model runs from G2_MIN_N rows on
 int launch_gemm_q4_256(const W4 &W, const void *x16, int n, const float *bias, float *y, hipStream_t s,
                        void *q16 = nullptr, const G2Epi *epi = nullptr);
 int launch_gemm_f16_256(const void *A16, int M, int K, const void *x16, int n, const float *bias, float *y,

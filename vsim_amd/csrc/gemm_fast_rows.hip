@@ -34,8 +34,6 @@
 #include "kern.hpp"
 #include "../../include/vsim_hip.h"
 
-#include <atomic>
-
 namespace vsim {
 
 constexpr int GF_RT = 16;      // weight rows per workgroup
@@ -128,22 +126,6 @@ __global__ void __launch_bounds__(GF_THREADS)
   }
 }
 
-namespace {
-std::atomic<int> g_batch_fast_gemm{1};  // vsim_batch_set_fast_gemm
-// from this many rows on the products of a fast batched step run on k_gemm_fast_rows by default: the
-// smallest measured B at which it beats the per-row launches by more than 5 % at both measured
-// shapes (profiles/batch_fast_bench.txt: GPT-J-6B 1.07x at B = 2, 1.58x at 4;
-// batch_fast_bench_pythia12b.txt: 0.78x at B = 2, 1.18x at 4)
-constexpr int BATCH_FAST_GEMM_MIN_N = 4;
-}  // namespace
-
-int batch_set_fast_gemm(int enable) { return g_batch_fast_gemm.exchange(enable < 0 || enable > 2 ? 1 : enable); }
-
-bool batch_fast_gemm_rows(int n) {
-  const int gm = g_batch_fast_gemm.load();
-  return gm == 2 || (gm == 1 && n >= BATCH_FAST_GEMM_MIN_N);
-}
-
 // y[j][m] = k_gemv_fast's value of weight row m and activation row j (+ bias[m]) for j < n <= 32,
 // on k_gemm_fast_rows or as one k_gemv_fast launch per row (vsim_batch_set_fast_gemm): the same bits
 int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s) {
@@ -151,22 +133,11 @@ int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias,
     set_error("q4_gemm_fast_rows: 1..32 activation rows, K a multiple of 32, w, xq and y required");
     return VSIM_EINVAL;
   }
-  const int nb = W.nb();
+  const ProductPlan pl = product_plan({.kind = BatchKind::ROWS_FAST, .mode = VSIM_MODE_FAST, .N = n, .M = W.rows,
+                                       .K = W.k, .fast_gemm = batch_fast_gemm()});
+  if (pl.kernel == ProductKernel::GEMV_FAST) return launch_gemv_rows(W, xq, nullptr, n, 1, bias, y, VSIM_MODE_FAST, s);
   const uint8_t *xqs = (const uint8_t *)xq;
-  const float *xdd = (const float *)(xqs + (size_t)n * nb * 16);
-  if (!batch_fast_gemm_rows(n)) {
-    for (int j = 0; j < n; ++j) {
-      GemvBatch B{};
-      B.nj = 1;
-      B.j[0].w = W;
-      B.j[0].xqs = xqs + (size_t)j * nb * 16;
-      B.j[0].xdd = xdd + (size_t)j * nb;
-      B.j[0].bias = bias;
-      B.j[0].y = y + (size_t)j * W.rows;
-      if (int rc = launch_gemv_batch(B, VSIM_MODE_FAST, s)) return rc;
-    }
-    return VSIM_OK;
-  }
+  const float *xdd = (const float *)(xqs + (size_t)n * W.nb() * 16);
   const dim3 grid((W.rows + GF_RT - 1) / GF_RT);
   if (n <= 16)
     hipLaunchKernelGGL((k_gemm_fast_rows<1>), grid, dim3(GF_THREADS), 0, s, W, xqs, xdd, n, bias, y);

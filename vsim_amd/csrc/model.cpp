@@ -9,7 +9,8 @@
 //
 // What the host side keeps is described once each: what distinguishes the three graphs
 // (GraphDesc: the one prompt layer, run_layer, the head and the decode steps branch on it), the
-// operands of a prompt product (Product: PromptBatch::mm picks the kernel), the tensors of an
+// operands of a prompt product (Product), what kind of batch runs the layers (BatchDesc) and which
+// kernel then runs a product (product_plan.hpp: PromptBatch::mm switches on its answer), the tensors of an
 // architecture (arch_table: plan_slots and bind_pointers walk it), the scratch buffers (scratch_table:
 // allocated, freed and poisoned from it), the five single-token step graphs (StepGraph
 // step[5], captured by decode_graph) and what a step of each kind enqueues (enqueue_step:
@@ -646,6 +647,39 @@ int prof_collect(vsim_model *m) {
 
 double w4_algo_bytes(const W4 &w) { return (double)w.rows * w.k / QK * QBYTES; }
 
+// The heads of one decode step's layer (attn.hpp) on this layer's Q / K / V rows in Qb / Kb / Vb:
+// the attention output leaves quantized in oq_qs / oq_d with its factors in oxd, every head over
+// nsplit workgroups.  kc / vc / npast: the layer's cache and the device position of the
+// single-token step; null for a rows batch, whose rows each have their own (AttnRows).
+AttnJob decode_attn_job(const vsim_model *m, const DevTables &tab, uint8_t *oq_qs, float *oq_d, float *oxd, int nsplit,
+                        float *kc, float *vc, const int *npast) {
+  const GraphDesc &G = m->gd;
+  const int E = m->hp.n_embd, H = m->hp.n_head;
+  AttnJob A{};
+  A.q = m->Qb;
+  A.k = m->Kb;
+  A.v = m->Vb;
+  A.kc = kc;
+  A.vc = vc;
+  A.npast = npast;
+  A.cs = m->rope_cs;
+  A.etab = tab.exp_f16;
+  A.d = E / H;
+  A.H = H;
+  A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
+  A.style = G.rotary == ROT_GPTJ ? 1 : 0;
+  A.n_ctx = m->n_ctx;
+  A.nsplit = nsplit;
+  A.scale = m->attn_scale != 0.0f ? m->attn_scale : (float)(1.0f / std::sqrt((double)(float(E) / H)));
+  A.kqv_nth = m->kqv_nth;
+  A.alibi = G.alibi ? m->alibi : nullptr;
+  A.oq_qs = oq_qs;
+  A.oq_d = oq_d;
+  A.oxd = oxd;
+  A.out = nullptr;
+  return A;
+}
+
 // One product of a Q4_0 weight with the batch's activation rows (PromptBatch::mm).  Every operand
 // defaults to absent; a call site names what it sets (designated initializers, in this order).
 struct Product {
@@ -668,38 +702,38 @@ struct Product {
   bool fused = false;          // out: the GELU-quantize or the G2Epi epilogue ran
 };
 
-// One prompt batch on its way through the layers and the head: N rows at n_past, counting its
-// launches into nk.
+// What a batch of N rows on its way through the layers and the head is, said once by the caller
+// (designated initializers, in this order) and read by enqueue_prompt, run_layer and run_head.
+struct BatchDesc {
+  BatchKind kind = BatchKind::PROMPT;
+  int N = 1;
+  int n_past = 0;  // the prompt kinds' position (a rows batch has one per row, in `rows`)
+  // the prompt kinds' KV cache ([layers][n_ctx][E] each): the model's own or a sequence slot's
+  float *kcache = nullptr, *vcache = nullptr;
+  // the rows kinds' per-row slot cache bases and positions, on the device
+  const BatchWords *rows = nullptr;
+  // The products' mode: the model's for a prompt; the call's for a rows batch (decode_batch is
+  // exact, decode_batch_fast fast, whatever the model's mode)
+  int mode = VSIM_MODE_EXACT;
+  const char *who = "";  // prefixes the error messages
+};
+
+// A batch on its way through the layers and the head, counting its launches into nk.  What
+// follows from the descriptor is derived here (pf) and in product_plan (the products' kernels).
 struct PromptBatch {
   vsim_model *m;
-  int N, n_past;
+  const BatchDesc &D;
+  const int N;
   int &nk;
-  // fast-mode batch: every activation goes once from f32 to the GEMM's fp16 operand
+  // fast-mode prompt batch: every activation goes once from f32 to the GEMM's fp16 operand
   // (quantize_row_q4_0 values, k_act_quant_f16; the GELU folded into fc_out's), in the model's
-  // scratch pf_x16: xa [N][E] norm outputs, then xb [N][F] attention / GELU outputs
+  // scratch pf_x16: xa [N][E] norm outputs, then xb [N][F] attention / GELU outputs.  A rows
+  // batch keeps the Q4 rows at every N.
   bool pf;
   void *xa, *xb;
-  // the KV cache the layers read and write ([layers][n_ctx][E] each): slot 0 unless the caller
-  // names another sequence slot (vsim_model_eval_seq)
-  float *kcache, *vcache;
-  // Batched decode step (vsim_model_decode_batch): the N rows are one token each of N sequences.
-  // rows non-null: each row's slot cache bases and position on the device, and the attention is
-  // launch_attn_decode_batch (n_past and kcache / vcache above go unused).  rows_gemm: the exact
-  // products run on k_gemm_exact_rows instead of launch_q4_gemv's dispatch (vsim_batch_set_gemm).
-  const BatchWords *rows = nullptr;
-  bool rows_gemm = false;
-  // The products' mode: the model's, or the call's for a rows batch (decode_batch is exact,
-  // decode_batch_fast fast, whatever the model's mode).  A fast rows batch (its layers and its
-  // head) keeps the Q4 rows at every N -- never the fp16 operands of a prompt batch -- and runs
-  // its products through launch_gemm_fast_rows.
-  int mode;
-  bool fast_rows;
-  PromptBatch(vsim_model *m_, int N_, int n_past_, int &nk_, int rows_mode = -1)
-      : m(m_), N(N_), n_past(n_past_), nk(nk_),
-        pf(rows_mode < 0 && m_->mode == VSIM_MODE_FAST && N_ >= GEMM_MIN_N && m_->pf_x16),
-        xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N_ * E_(m_)) : nullptr),
-        kcache(m_->kcache), vcache(m_->vcache), mode(rows_mode < 0 ? m_->mode : rows_mode),
-        fast_rows(rows_mode == VSIM_MODE_FAST) {}
+  PromptBatch(vsim_model *m_, const BatchDesc &D_, int &nk_)
+      : m(m_), D(D_), N(D_.N), nk(nk_), pf(!is_rows(D_.kind) && f16_gemm_rows(D_.mode, D_.N) && m_->pf_x16),
+        xa(pf ? m_->pf_x16 : nullptr), xb(pf ? (void *)((uint16_t *)m_->pf_x16 + (size_t)N * E_(m_)) : nullptr) {}
 
   int act16(const float *x, int K, void *x16, const float *gbias, bool gelu) {
     if (!pf) return VSIM_OK;
@@ -711,46 +745,39 @@ struct PromptBatch {
     ++nk;
     return pf ? launch_norm_f16q(x, x16, E_(m), N, w, b, m->stream) : launch_norm(x, y, E_(m), N, w, b, m->stream);
   }
-  // Quantize the activation (unless it is an fp16 operand already) and run the product in the
-  // model's mode.
+  // Quantize the activation (unless it is an fp16 operand already) and run the product on the
+  // kernel product_plan names.
   int mm(Product &P) {
     const int M = P.w.rows, K = P.w.k;
-    P.fused = false;
+    hipStream_t s = m->stream;
+    const ProductPlan pl = product_plan({.kind = D.kind, .mode = D.mode, .N = N, .M = M, .K = K, .x16 = P.x16 != nullptr,
+                                         .gelu = P.gq && P.gq_bias, .epi = P.epi != nullptr, .gemm = batch_gemm(),
+                                         .fast_gemm = batch_fast_gemm()});
+    P.fused = pl.fused;
+    if (pl.error) { set_error(pl.error); return VSIM_EINVAL; }
     if (P.quantize && !P.x16) {
-      RC(launch_q4_quantize(P.x, K, N, P.xq, P.xd, m->stream));
+      RC(launch_q4_quantize(P.x, K, N, P.xq, P.xd, s));
       ++nk;
     }
-    // long prompt: the 256-wide-tile GEMM, the Q4_0 weight dequantized to fp16 in LDS
-    if (P.x16 && N >= G2_MIN_N && K % 64 == 0) {
-      const bool gelu = P.gq && P.gq_bias && M % QK == 0;
-      LAUNCH(m, nk,
-             launch_gemm_q4_256(P.w, P.x16, N, gelu ? P.gq_bias : P.bias, P.y, m->stream, gelu ? P.gq : nullptr,
-                                gelu ? nullptr : P.epi),
-             P.what ? P.what : "k_gemm_f16_256 (prompt)", w4_algo_bytes(P.w));
-      P.fused = gelu || P.epi;
-      return VSIM_OK;
+    const long ev = prof_begin(m);
+    switch (pl.kernel) {
+      case ProductKernel::GEMM_F16_256:
+        RC(launch_gemm_q4_256(P.w, P.x16, N, pl.gelu ? P.gq_bias : P.bias, P.y, s, pl.gelu ? P.gq : nullptr,
+                              pl.gelu ? nullptr : P.epi));
+        break;
+      case ProductKernel::GEMM_F16:
+        RC(P.x16 ? launch_gemm_f16x(P.w, P.x16, N, P.bias, P.y, s) : launch_gemm_q4_f16(P.w, P.xq, N, P.bias, P.y, s));
+        break;
+      case ProductKernel::GEMM_EXACT: RC(launch_gemm_exact(P.w, P.xd, N, P.bias, P.y, s)); break;
+      case ProductKernel::GEMM_EXACT_ROWS: RC(launch_gemm_exact_rows(P.w, P.xd, N, P.bias, P.y, s)); break;
+      // (launch_gemm_fast_rows asks the same plan of the same switch: vsim_op_q4_gemm_fast_rows' contract)
+      case ProductKernel::GEMM_FAST_ROWS: RC(launch_gemm_fast_rows(P.w, P.xq, N, P.bias, P.y, s)); break;
+      case ProductKernel::GEMV_CHAIN: RC(launch_gemv_rows(P.w, P.xq, P.xd, N, GEMV_JOBS, P.bias, P.y, D.mode, s)); break;
+      case ProductKernel::GEMV_FAST: RC(launch_gemv_rows(P.w, P.xq, P.xd, N, 1, P.bias, P.y, D.mode, s)); break;
+      case ProductKernel::NONE: break;
     }
-    // fast batched decode step: k_gemv_fast's value of every row, on k_gemm_fast_rows (one pass of
-    // the weight for all rows) or as one launch per row (vsim_batch_set_fast_gemm): the same bits
-    if (fast_rows) {
-      if (P.x16 || N > VSIM_BATCH_MAX) { set_error("fast batched step: a product left the Q4 rows"); return VSIM_EINVAL; }
-      LAUNCH(m, nk, launch_gemm_fast_rows(P.w, P.xq, N, P.bias, P.y, m->stream),
-             P.what ? P.what : batch_fast_gemm_rows(N) ? "k_gemm_fast_rows (batch)" : "k_gemv_fast (batch, per row)",
-             w4_algo_bytes(P.w) * (batch_fast_gemm_rows(N) ? 1 : N));
-      if (!batch_fast_gemm_rows(N)) nk += N - 1;
-      return VSIM_OK;
-    }
-    // batched decode step, exact mode: every weight block dequantized once for all the rows
-    if (rows_gemm && !P.x16 && mode == VSIM_MODE_EXACT && N <= VSIM_BATCH_MAX) {
-      LAUNCH(m, nk, launch_gemm_exact_rows(P.w, P.xd, N, P.bias, P.y, m->stream),
-             P.what ? P.what : "k_gemm_exact_rows (batch)", w4_algo_bytes(P.w));
-      return VSIM_OK;
-    }
-    LAUNCH(m, nk,
-           P.x16 ? launch_gemm_f16x(P.w, P.x16, N, P.bias, P.y, m->stream)
-                 : launch_q4_gemv(P.w.qs, M, K, P.xq, P.xd, N, P.bias, P.y, mode, m->stream),
-           P.what ? P.what : P.x16 ? "k_gemm_f16 (prompt)" : N > 1 ? "gemv (prompt rows)" : "gemv (general path)",
-           w4_algo_bytes(P.w));
+    if (ev >= 0) prof_end(m, ev, P.what ? P.what : pl.name, w4_algo_bytes(P.w) * pl.passes);
+    nk += pl.kernels;
     return VSIM_OK;
   }
 };
@@ -764,15 +791,17 @@ int run_layer(PromptBatch &B, int il) {
   vsim_model *m = B.m;
   const GraphDesc &G = m->gd;
   const LayerW &L = m->layers[il - m->l0];
-  const int N = B.N, n_past = B.n_past, E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
+  const BatchDesc &D = B.D;
+  const bool rows = is_rows(D.kind);
+  const int N = D.N, n_past = D.n_past, E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
   int &nk = B.nk;
   hipStream_t s = m->stream;
   RC(B.norm(m->inpL, m->cur1, L.ln1_w, L.ln1_b, B.xa));
   const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
-  float *kc = B.kcache + loff, *vc = B.vcache + loff;
+  float *kc = rows ? nullptr : D.kcache + loff, *vc = rows ? nullptr : D.vcache + loff;
   // long GPT-J prompt: RoPE and the KV-cache write (vsim.cpp:553-580) in the Q/K/V GEMMs'
   // epilogues -- K and V straight into their cache rows -- instead of a pass of their own
-  const bool g2 = B.pf && N >= G2_MIN_N && E % 64 == 0;
+  const bool g2 = wide_gemm(B.pf, N, E);  // (the layer's products: K = E, or 4 E for fc_out)
   const bool rope_epi = g2 && G.rotary == ROT_GPTJ;
   G2Epi er;
   er.cs = m->rope_cs;
@@ -783,7 +812,7 @@ int run_layer(PromptBatch &B, int il) {
   // ... and the new keys' fp16 copies for the prompt attention (K rows, V^T columns), which
   // then converts only the cached keys before them.  (ALiBi lives in the softmax kernel only:
   // BLOOM keeps the KQ / softmax / KQV kernels in both modes.)
-  const bool attn16 = !B.rows && !G.alibi && B.mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
+  const bool attn16 = !rows && !G.alibi && D.mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
   if (attn16) RC(ensure_pf_scratch(m));
   const bool kv16_epi = rope_epi && attn16;
   G2Epi ek = er, ev;
@@ -812,32 +841,15 @@ int run_layer(PromptBatch &B, int il) {
   }
   RC(B.mm(v));
   const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
-  if (B.rows) {
+  if (rows) {
     // batched decode step: RoPE, the cache write, KQ, softmax, KQV and the out-projection's
     // activation quantize of every row in one launch, each row on its own cache at its own
     // position (attn.hpp, the single-token step's head); Q4 rows in launch_q4_quantize's layout
     DevTables tab;
     RC(tables_get(&tab));
-    AttnJob A{};
-    A.q = m->Qb;
-    A.k = m->Kb;
-    A.v = m->Vb;
-    A.cs = m->rope_cs;
-    A.etab = tab.exp_f16;
-    A.d = d;
-    A.H = H;
-    A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
-    A.style = G.rotary == ROT_GPTJ ? 1 : 0;
-    A.n_ctx = m->n_ctx;
-    A.nsplit = 1;
-    A.scale = m->attn_scale != 0.0f ? m->attn_scale : scale;
-    A.kqv_nth = m->kqv_nth;
-    A.alibi = G.alibi ? m->alibi : nullptr;
-    A.oq_qs = m->xq2;
-    A.oq_d = (float *)(m->xq2 + (size_t)N * (E / QK) * 16);
-    A.oxd = m->xd2;
-    A.out = nullptr;
-    const AttnRows R{B.rows->kc, B.rows->vc, loff, B.rows->npast};
+    const AttnJob A = decode_attn_job(m, tab, m->xq2, (float *)(m->xq2 + (size_t)N * (E / QK) * 16), m->xd2, 1,
+                                      nullptr, nullptr, nullptr);
+    const AttnRows R{D.rows->kc, D.rows->vc, loff, D.rows->npast};
     LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
   } else if (!rope_epi) {
     RC(launch_rope_kv_write(G.rotary == ROT_GPTJ ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past,
@@ -848,7 +860,7 @@ int run_layer(PromptBatch &B, int il) {
   const int nkv = n_past + N;
   // (head dim 256: the attention writes the out-projection's fp16 operand itself)
   const bool attn_q16 = attn16 && B.pf && attn_prefill_quantizes(d);
-  if (B.rows) {
+  if (rows) {
     // (done above, the out-projection's Q4 rows included)
   } else if (attn16) {
     // fast-mode prompt: one-pass fp16 MFMA attention (attn_prefill.hip)
@@ -861,7 +873,7 @@ int run_layer(PromptBatch &B, int il) {
     RC(launch_kqv(vc, E, m->kq, d, H, nkv, N, m->attn_in, 1, s, n_past)); ++nk;
   }
   if (!attn_q16) RC(B.act16(m->attn_in, E, B.xb, nullptr, false));
-  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = !B.rows,
+  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = !rows,
             .bias = G.qkvo_bias ? L.bo : nullptr, .y = m->attn, .x16 = B.xb};
   RC(B.mm(o));
   // fc_in (its bias goes with the GELU) reads the input norm's quantized row again, or the MLP's
@@ -1068,7 +1080,6 @@ int enqueue_decode(vsim_model *m, int &nk) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
   }
-  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
   // algorithmic bytes of the profiled launches: KV rows read (P + 1) and
   // written by the attention, rows of E floats read / written by the LayerNorm step
   const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
@@ -1107,49 +1118,28 @@ int enqueue_decode(vsim_model *m, int &nk) {
   // the next layer's LayerNorm inside the tail (TailLn; parallel-residual graphs: the tail is
   // where both branches of the layer end)
   const bool lnt_ok = tail && !serial && m->l1 <= 255 && tail_ln_ok(E);
+  // each head over two workgroups (its KQV columns halved; the scores computed by both) in the
+  // parallel-residual fused tail, where it was measured: r05, 248-token GPT-J lines 608.9 / 612.5
+  // vs 606.9 / 610.8 tok/s unsplit, 602.6 / 601.3 at four (profiles/r05_tail_variants_ab.txt).
+  // The largest split <= ATT_SPLIT whose column parts are whole 32-blocks; the serial graphs'
+  // heads and the standalone k_attn_decode stay one workgroup per head.  (A/B builds:
+  // tools/build_variant.sh NAME model.cpp 's/ATT_SPLIT = 2/ATT_SPLIT = 1/'.)
+  constexpr int ATT_SPLIT = 2;
+  int nsplit = 1;
+  for (int sp = tail && !serial ? ATT_SPLIT : 1; sp > 1; --sp)
+    if (d % sp == 0 && (d / sp) % QK == 0) {
+      nsplit = sp;
+      break;
+    }
   auto attn_job = [&](size_t loff) {
-    AttnJob A{};
-    A.q = m->Qb;
-    A.k = m->Kb;
-    A.v = m->Vb;
-    A.kc = m->kcache + loff;
-    A.vc = m->vcache + loff;
-    A.npast = m->npast_dev;
-    A.cs = m->rope_cs;
-    A.etab = tab.exp_f16;
-    A.d = d;
-    A.H = H;
-    A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
-    A.style = G.rotary == ROT_GPTJ ? 1 : 0;
-    A.n_ctx = m->n_ctx;
-    // each head over two workgroups (its KQV columns halved; the scores computed by both) in the
-    // parallel-residual fused tail, where it was measured: r05, 248-token GPT-J lines 608.9 / 612.5
-    // vs 606.9 / 610.8 tok/s unsplit, 602.6 / 601.3 at four (profiles/r05_tail_variants_ab.txt).
-    // The largest split <= ATT_SPLIT whose column parts are whole 32-blocks; the serial graphs'
-    // heads and the standalone k_attn_decode stay one workgroup per head.  (A/B builds:
-    // tools/build_variant.sh NAME model.cpp 's/ATT_SPLIT = 2/ATT_SPLIT = 1/'.)
-    constexpr int ATT_SPLIT = 2;
-    A.nsplit = 1;
-    for (int sp = tail && !serial ? ATT_SPLIT : 1; sp > 1; --sp)
-      if (d % sp == 0 && (d / sp) % QK == 0) {
-        A.nsplit = sp;
-        break;
-      }
-    A.scale = m->attn_scale != 0.0f ? m->attn_scale : scale;
-    A.kqv_nth = m->kqv_nth;
-    A.alibi = G.alibi ? m->alibi : nullptr;
-    A.oq_qs = qa;
-    A.oq_d = da;
-    A.oxd = m->xda;
-    A.out = nullptr;
-    return A;
+    return decode_attn_job(m, tab, qa, da, m->xda, nsplit, m->kcache + loff, m->vcache + loff, m->npast_dev);
   };
-  auto gemv = [&](const GemvBatch &Bt, const char *what, double bytes) -> int {
+  // (exact_kernel: the exact kernel's name as the profile has always had it for this product,
+  // where it does not ask gemv_chain_solo)
+  auto gemv = [&](const GemvBatch &Bt, const char *what, double bytes, const char *exact_kernel = nullptr) -> int {
+    if (!exact_kernel) exact_kernel = gemv_chain_solo(Bt) ? "k_gemv_solo" : "k_gemv_chain32";
     LAUNCH(m, nk, launch_gemv_epi(Bt, m->mode, s),
-           std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : gemv_chain_solo(Bt) ? "k_gemv_solo"
-                                                                                       : "k_gemv_chain32") +
-               " (" + what + ")",
-           bytes);
+           std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : exact_kernel) + " (" + what + ")", bytes);
     return VSIM_OK;
   };
   for (int il = m->l0; il < m->l1; ++il) {
@@ -1236,9 +1226,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
     job(B, 1, L.wq, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bq : nullptr, m->Qb);
     job(B, 2, L.wk, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bk : nullptr, m->Kb);
     job(B, 3, L.wv, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bv : nullptr, m->Vb);
-    LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
-           m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (fc_in, Q, K, V)" : "k_gemv_fast_epi (fc_in, Q, K, V)",
-           w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w));
+    RC(gemv(B, "fc_in, Q, K, V", w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w), "k_gemv_solo"));
     // 3. attention for the new token (attn.hpp), fc_out and the out-projection
     const AttnJob A = attn_job(loff);
     GemvBatch Bf{}, Bo{};
@@ -1293,9 +1281,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
       LAUNCH(m, nk, launch_attn_decode(A, m->n_ctx, s), "k_attn_decode", kv_bytes);
       Bf.j[1] = Bo.j[0];
       Bf.nj = 2;
-      LAUNCH(m, nk, launch_gemv_epi(Bf, m->mode, s),
-             m->mode == VSIM_MODE_EXACT ? "k_gemv_chain32 (fc_out, out-proj)" : "k_gemv_fast_epi (fc_out, out-proj)",
-             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bf.j[1].w));
+      RC(gemv(Bf, "fc_out, out-proj", w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bf.j[1].w), "k_gemv_chain32"));
     }
     pending = true;
     pend_a = m->attn;
@@ -1312,8 +1298,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
     GemvBatch B{};
     B.nj = 1;
     job(B, 0, m->lmh, V, E, m->xd1, q1, d1, G.lmh_bias ? m->lmh_b : nullptr, m->logits);
-    LAUNCH(m, nk, launch_gemv_epi(B, m->mode, s),
-           m->mode == VSIM_MODE_EXACT ? "k_gemv_solo (lm_head)" : "k_gemv_fast_epi (lm_head)", w4_algo_bytes(B.j[0].w));
+    RC(gemv(B, "lm_head", w4_algo_bytes(B.j[0].w), "k_gemv_solo"));
   } else if (pending) {
     RC(launch_residual_join(R[cur], pend_a, pend_ab, m->ff, pend_fb, R[cur ^ 1], E, s));
     ++nk;
@@ -1989,21 +1974,16 @@ int run_step(vsim_model *m, StepKind kind, bool graph, int &nk, bool want_logits
   return VSIM_OK;
 }
 
-// The general path up to the head (prompt batches; scoring at every N): the embedding of
-// `tokens` (first stage) or the residual from resid_in, then this stage's layers; the rows'
-// residual ends in inpL.  `who` prefixes the error messages.
-// kc / vc: the sequence slot's caches (null: slot 0).  rows (the batched decode step): the N
-// tokens are one each of N sequences, every row on its slot at its position (n_past unused);
-// rows_gemm and rows_mode (the products' mode of a rows batch; -1: the model's) as PromptBatch's.
-int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, const float *resid_in, int &nk,
-                   const char *who, float *kc = nullptr, float *vc = nullptr, const BatchWords *rows = nullptr,
-                   bool rows_gemm = false, int rows_mode = -1) {
-  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+// The general path up to the head for the batch D describes (prompt batches; scoring at every N;
+// the batched decode steps): the embedding of its D.N `tokens` (first stage) or the residual from
+// resid_in, then this stage's layers; the rows' residual ends in inpL.
+int enqueue_prompt(vsim_model *m, const BatchDesc &D, const int32_t *tokens, const float *resid_in, int &nk) {
+  const int E = m->hp.n_embd, V = m->hp.n_vocab, N = D.N;
   hipStream_t s = m->stream;
   if (m->first) {
-    if (!tokens) { set_error(std::string(who) + ": first stage needs tokens"); return VSIM_EINVAL; }
+    if (!tokens) { set_error(std::string(D.who) + ": first stage needs tokens"); return VSIM_EINVAL; }
     for (int i = 0; i < N; ++i) {
-      if (tokens[i] < 0 || tokens[i] >= V) { set_error(std::string(who) + ": token id out of range"); return VSIM_EINVAL; }
+      if (tokens[i] < 0 || tokens[i] >= V) { set_error(std::string(D.who) + ": token id out of range"); return VSIM_EINVAL; }
       m->tok_host[i] = tokens[i];
     }
     VSIM_HIP(hipMemcpyAsync(m->tok_dev, m->tok_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -2016,31 +1996,48 @@ int enqueue_prompt(vsim_model *m, int n_past, const int32_t *tokens, int N, cons
       ++nk;
     }
   } else {
-    if (!resid_in) { set_error(std::string(who) + ": non-first stage needs resid_in"); return VSIM_EINVAL; }
+    if (!resid_in) { set_error(std::string(D.who) + ": non-first stage needs resid_in"); return VSIM_EINVAL; }
     VSIM_HIP(hipMemcpyAsync(m->inpL, resid_in, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
   }
-  PromptBatch B(m, N, n_past, nk, rows ? rows_mode : -1);
-  if (kc) B.kcache = kc;
-  if (vc) B.vcache = vc;
-  B.rows = rows;
-  B.rows_gemm = rows_gemm;
+  PromptBatch B(m, D, nk);
   for (int il = m->l0; il < m->l1; ++il) RC(run_layer(B, il));
   return VSIM_OK;
 }
 
-// The head for `rows` rows of the residual from x: the final LayerNorm and the lm_head product
-// (+ GPT-J's bias) into out ([rows][n_vocab]).  The row count picks the product as for any prompt
-// GEMM: exact mode the row-exact GEMV / GEMM (rows independent of their neighbours); fast mode the
-// fp16 MFMA GEMM on launch_norm_f16q's operand from GEMM_MIN_N rows, else quantize + GEMV.
-// rows_mode >= 0: the head of a batched decode step in that mode (PromptBatch).
-int run_head(vsim_model *m, const float *x, int rows, float *out, const char *what, int &nk, bool rows_gemm = false,
-             int rows_mode = -1) {
-  PromptBatch B(m, rows, 0, nk, rows_mode);
-  B.rows_gemm = rows_gemm;
+// The head for the D.N rows of the residual from x: the final LayerNorm and the lm_head product
+// (+ GPT-J's bias) into out ([D.N][n_vocab]), profiled as `what`.  The batch's kind, mode and row
+// count pick the product as for any other (product_plan): exact mode the row-exact GEMV / GEMM
+// (rows independent of their neighbours); a fast-mode prompt the fp16 MFMA GEMM on
+// launch_norm_f16q's operand from GEMM_MIN_N rows, else quantize + GEMV; a batched step its rows'.
+int run_head(vsim_model *m, const BatchDesc &D, const float *x, float *out, const char *what, int &nk) {
+  PromptBatch B(m, D, nk);
   RC(B.norm(x, m->cur1, m->lnf_w, m->lnf_b, B.xa));
   Product P{.w = w4_view(m->lmh, m->hp.n_vocab, E_(m)), .x = m->cur1, .xq = m->xq1, .xd = m->xd1, .quantize = true,
             .bias = m->gd.lmh_bias ? m->lmh_b : nullptr, .y = out, .x16 = B.xa, .what = what};
   return B.mm(P);
+}
+
+// The head of the prompt kinds' last row, which alone leaves an eval (vsim.cpp:736-737; rows are
+// independent): one row, so the f32 norm and the GEMV in both modes
+int run_last_row_head(vsim_model *m, const BatchDesc &D, int &nk) {
+  const BatchDesc one{.kind = D.kind, .N = 1, .mode = D.mode, .who = D.who};
+  return run_head(m, one, m->inpL + (size_t)(D.N - 1) * E_(m), m->logits, nullptr, nk);
+}
+
+// Can the device make this sampler's candidates (k_sample_topk's limits)?  Otherwise: the logits
+// and the reference's host code.
+bool sampler_on_device(const vsim_sampler *sm, int V) {
+  return !(sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX || !(sm->temp > 0.0) ||
+           !(sm->repeat_penalty > 0.0));
+}
+// The sampler's parameter block; for one whose row takes the host path, one candidate of an
+// empty window, which nobody reads
+void fill_topk_params(TopkParams *pb, const vsim_sampler *sm, bool on_dev) {
+  pb->scale = on_dev ? 1.0 / sm->temp : 1.0;
+  pb->penalty = on_dev ? sm->repeat_penalty : 1.0;
+  pb->k = on_dev ? sm->top_k : 1;
+  pb->nw = on_dev ? (int32_t)sm->win.size() : 0;
+  if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
 }
 
 // The end of a call that waits for its work: the bounded waits' word read back, the stream
@@ -2080,10 +2077,6 @@ int begin_single(vsim_model *m, const char *who, int n_past, int steps, const ch
   return VSIM_OK;
 }
 
-std::atomic<int> g_batch_gemm{1};        // vsim_batch_set_gemm
-// from this many rows on a batched step's products run on k_gemm_exact_rows by default: below it
-// the GEMV jobs are faster (profiles/batch_decode_bench.txt)
-constexpr int BATCH_GEMM_MIN_N = 12;
 std::atomic<int> g_score_chunk_rows{0};  // vsim_score_set_chunk_rows (0: default)
 constexpr size_t SCORE_SCRATCH_BYTES = (size_t)64 << 20;
 constexpr int SCORE_MIN_ROWS = 8, SCORE_MAX_ROWS = 256;
@@ -2133,21 +2126,14 @@ int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t 
   if (!m || !sm || !next_token) { set_error("eval_sample: null argument"); return VSIM_EINVAL; }
   RC(begin_single(m, "eval_sample", n_past, 1, "1", token));
   const int V = m->hp.n_vocab;
-  // outside the device stage's limits: the logits step and the reference's host code
-  if (sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX || !(sm->temp > 0.0) ||
-      !(sm->repeat_penalty > 0.0)) {
+  if (!sampler_on_device(sm, V)) {  // the logits step and the reference's host code
     std::vector<float> lg((size_t)V);
     RC(vsim_model_eval(m, n_past, &token, 1, nullptr, nullptr, lg.data()));
     return vsim_sampler_sample_host(sm, lg.data(), V, next_token);
   }
   if (sm->top_k < 1) { set_error("eval_sample: top_k < 1"); return VSIM_EINVAL; }
   const ErrScope es(m);
-  TopkParams *pb = m->sp_host;
-  pb->scale = 1.0 / sm->temp;
-  pb->penalty = sm->repeat_penalty;
-  pb->k = sm->top_k;
-  pb->nw = (int32_t)sm->win.size();
-  if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
+  fill_topk_params(m->sp_host, sm, true);
   int nk = 0;
   RC(run_step(m, STEP_SAMPLE, m->graph_enabled, nk));
   RC(finish_call(m, nk));
@@ -2182,7 +2168,7 @@ int vsim_model_reserve(vsim_model *m, int n_tokens) {
     RC(ensure_pf_scratch(m));
     RC(attn_prefill_prepare());
   }
-  if (n_tokens >= G2_MIN_N) RC(gemm_reserve_stream(m->stream));
+  if (wide_gemm(true, n_tokens, E)) RC(gemm_reserve_stream(m->stream));
   VSIM_HIP(hipStreamSynchronize(m->stream));
   return VSIM_OK;
 }
@@ -2213,11 +2199,11 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
     RC(run_step(m, STEP_LOGITS, m->graph_enabled && m->first && m->last, nk, logits != nullptr, resid_out));
   } else {
     // general path: prompt batches (N > 1)
-    RC(enqueue_prompt(m, n_past, tokens, N, resid_in, nk, "eval"));
+    const BatchDesc D{.kind = BatchKind::PROMPT, .N = N, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
+                      .mode = m->mode, .who = "eval"};
+    RC(enqueue_prompt(m, D, tokens, resid_in, nk));
     if (m->last) {
-      // only the last row's logits leave the eval (vsim.cpp:736-737); rows are independent
-      // (one row: the f32 norm and the GEMV in both modes)
-      RC(run_head(m, m->inpL + (size_t)(N - 1) * E, 1, m->logits, nullptr, nk));
+      RC(run_last_row_head(m, D, nk));
       if (logits) VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, s));
     } else if (resid_out) {
       VSIM_HIP(hipMemcpyAsync(resid_out, m->inpL, sizeof(float) * N * E, hipMemcpyDeviceToDevice, s));
@@ -2227,8 +2213,6 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   if (m->last && logits) memcpy(logits, m->logit_host, sizeof(float) * V);
   return VSIM_OK;
 }
-
-int vsim_batch_set_gemm(int enable) { return g_batch_gemm.exchange(enable < 0 || enable > 2 ? 1 : enable); }
 
 int vsim_model_seq_reserve(vsim_model *m, int n_seq) {
   if (!m) { set_error("seq_reserve: null model"); return VSIM_EINVAL; }
@@ -2282,10 +2266,12 @@ int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *token
   VSIM_HIP(hipSetDevice(m->device));
   const ErrScope es(m);
   RC(ensure_scratch(m, N));
-  const int E = m->hp.n_embd, V = m->hp.n_vocab;
+  const int V = m->hp.n_vocab;
   int nk = 0;
-  RC(enqueue_prompt(m, n_past, tokens, N, nullptr, nk, "eval_seq", slot_k(m, seq), slot_v(m, seq)));
-  RC(run_head(m, m->inpL + (size_t)(N - 1) * E, 1, m->logits, nullptr, nk));
+  const BatchDesc D{.kind = BatchKind::PROMPT_SLOT, .N = N, .n_past = n_past, .kcache = slot_k(m, seq),
+                    .vcache = slot_v(m, seq), .mode = m->mode, .who = "eval_seq"};
+  RC(enqueue_prompt(m, D, tokens, nullptr, nk));
+  RC(run_last_row_head(m, D, nk));
   if (logits) VSIM_HIP(hipMemcpyAsync(m->logit_host, m->logits, sizeof(float) * V, hipMemcpyDeviceToHost, m->stream));
   RC(finish_call(m, nk));
   if (logits) memcpy(logits, m->logit_host, sizeof(float) * V);
@@ -2325,8 +2311,7 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
     for (int a = 0; a < b; ++a)
       if (samplers[a] == sm) { set_error("decode_batch_sample: a sampler is named twice"); return VSIM_EINVAL; }
     if (sm->top_k < 1) { set_error("decode_batch_sample: top_k < 1"); return VSIM_EINVAL; }
-    on_dev[b] = !(sm->top_k > VSIM_TOPK_MAX || sm->top_k > V || sm->win.size() > (size_t)VSIM_WINDOW_MAX ||
-                  !(sm->temp > 0.0) || !(sm->repeat_penalty > 0.0));
+    on_dev[b] = sampler_on_device(sm, V);
     any_dev |= on_dev[b];
   }
   m->st_npast = -1;  // as an eval: a stage step needs a new stage_begin
@@ -2341,24 +2326,15 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
     m->bw_host->npast[b] = n_past[b];
   }
   VSIM_HIP(hipMemcpyAsync(m->bw_dev, m->bw_host, sizeof(BatchWords), hipMemcpyHostToDevice, s));
-  const int gm = g_batch_gemm.load();
-  const bool rows_gemm = mode == VSIM_MODE_EXACT && (gm == 2 || (gm == 1 && B >= BATCH_GEMM_MIN_N));
   int nk = 0;
-  RC(enqueue_prompt(m, 0, tokens, B, nullptr, nk, "decode_batch", nullptr, nullptr, m->bw_dev, rows_gemm, mode));
-  RC(run_head(m, m->inpL, B, m->score_x, "lm_head (batch)", nk, rows_gemm, mode));
+  const BatchDesc D{.kind = mode == VSIM_MODE_EXACT ? BatchKind::ROWS_EXACT : BatchKind::ROWS_FAST, .N = B,
+                    .rows = m->bw_dev, .mode = mode, .who = "decode_batch"};
+  RC(enqueue_prompt(m, D, tokens, nullptr, nk));
+  RC(run_head(m, D, m->inpL, m->score_x, "lm_head (batch)", nk));
   int32_t *am_dev = (int32_t *)m->score_out;
   if (samplers) {
-    // the rows' parameter blocks (only the B in use travel), one launch for all rows, the B lists back;
-    // a host-path row's block asks for one candidate of an empty window, which nobody reads
-    for (int b = 0; b < B; ++b) {
-      TopkParams *pb = m->bs_par_host + b;
-      const vsim_sampler *sm = samplers[b];
-      pb->scale = on_dev[b] ? 1.0 / sm->temp : 1.0;
-      pb->penalty = on_dev[b] ? sm->repeat_penalty : 1.0;
-      pb->k = on_dev[b] ? sm->top_k : 1;
-      pb->nw = on_dev[b] ? (int32_t)sm->win.size() : 0;
-      if (pb->nw) memcpy(pb->win, sm->win.data(), sizeof(int32_t) * sm->win.size());
-    }
+    // the rows' parameter blocks (only the B in use travel), one launch for all rows, the B lists back
+    for (int b = 0; b < B; ++b) fill_topk_params(m->bs_par_host + b, samplers[b], on_dev[b]);
     if (any_dev) {
       VSIM_HIP(hipMemcpyAsync(m->bs_par_dev, m->bs_par_host, sizeof(TopkParams) * B, hipMemcpyHostToDevice, s));
       LAUNCH(m, nk, launch_topk_rows(m->score_x, V, V, B, m->bs_par_dev, m->bs_out_dev, m->bs_ws, s),
@@ -2449,7 +2425,9 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
   RC(ensure_score_scratch(m, C));
   hipStream_t s = m->stream;
   int nk = 0;
-  RC(enqueue_prompt(m, n_past, tokens, N, resid_in, nk, "eval_score"));
+  const BatchDesc D{.kind = BatchKind::PROMPT, .N = N, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
+                    .mode = m->mode, .who = "eval_score"};
+  RC(enqueue_prompt(m, D, tokens, resid_in, nk));
   for (int i = 0; i < N; ++i) m->score_tgt_host[i] = targets ? targets[i] : -1;
   VSIM_HIP(hipMemcpyAsync(m->score_tgt, m->score_tgt_host, N * sizeof(int32_t), hipMemcpyHostToDevice, s));
   // the results of all rows: N doubles, then N ints (one copy out at the end)
@@ -2459,7 +2437,8 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
   // picks the product (run_head), so fast-mode bits may depend on C; exact mode's do not.
   for (int r0 = 0; r0 < N; r0 += C) {
     const int c = std::min(C, N - r0);
-    RC(run_head(m, m->inpL + (size_t)r0 * E, c, m->score_x, "lm_head (score)", nk));
+    const BatchDesc chunk{.kind = BatchKind::PROMPT, .N = c, .mode = m->mode, .who = "eval_score"};
+    RC(run_head(m, chunk, m->inpL + (size_t)r0 * E, m->score_x, "lm_head (score)", nk));
     LAUNCH(m, nk, launch_score_rows(m->score_x, V, c, m->score_tgt + r0, lp_dev + r0, am_dev + r0, s), "k_score_rows",
            (double)c * V * sizeof(float));
     if (logits_all)

@@ -215,39 +215,45 @@ int launch_gemv_batch(const GemvBatch &B, int mode, hipStream_t s) {
   return VSIM_OK;
 }
 
-// (GEMM_MIN_N, common.hpp: fast mode, from this many tokens on, the MFMA GEMM)
-
-int launch_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias, float *y,
-                   int mode, hipStream_t s) {
-  if (K % QK || M <= 0 || n <= 0) { set_error("q4_gemv: bad shape"); return VSIM_EINVAL; }
-  const W4 W = w4_view(w, M, K);
-  if (mode == VSIM_MODE_EXACT && !xd) { set_error("q4_gemv: exact mode needs xd"); return VSIM_EINVAL; }
-  // fast mode, prompt batches: fp16 MFMA GEMM after in-LDS dequant (gemm_f16.hip)
-  if (mode == VSIM_MODE_FAST && n >= GEMM_MIN_N) return launch_gemm_q4_f16(W, xq, n, bias, y, s);
-  // exact mode, prompt batches: the register-tiled chain GEMM (gemm_exact.hip).  Its 128-token
-  // tiles cost the same for 5 tokens as for 128 (r04 rocprof: 1.09 ms per GPT-J GEMM for a
-  // 5-token prompt), so short batches take the decode GEMV, up to 4 tokens per launch (one job
-  // each: the same chains, bit for bit)
-  if (mode == VSIM_MODE_EXACT && n > EXACT_GEMV_MAX_N) return launch_gemm_exact(W, xd, n, bias, y, s);
-  const size_t nbk = (size_t)n * (K / QK);
+// Rows [0, n) of Q4 activations xq (launch_q4_quantize's layout; xd: their factors, exact mode)
+// through the decode GEMV, `per` rows as the jobs of one launch: the same chains (exact) or the
+// same k_gemv_fast value (fast) as each row alone, bit for bit
+int launch_gemv_rows(const W4 &W, const void *xq, const float *xd, int n, int per, const float *bias, float *y, int mode,
+                     hipStream_t s) {
+  const int nb = W.nb();
   const uint8_t *xqs = (const uint8_t *)xq;
-  const float *xdd = (const float *)(xqs + nbk * 16);
-  const int per = mode == VSIM_MODE_EXACT ? 4 : 1;
+  const float *xdd = (const float *)(xqs + (size_t)n * nb * 16);
   for (int i0 = 0; i0 < n; i0 += per) {
     GemvBatch B{};
     B.nj = std::min(per, n - i0);
     for (int u = 0; u < B.nj; ++u) {
       const int ic = i0 + u;
       B.j[u].w = W;
-      B.j[u].xd = xd ? xd + (size_t)ic * K : nullptr;
-      B.j[u].xqs = xqs + (size_t)ic * (K / QK) * 16;
-      B.j[u].xdd = xdd + (size_t)ic * (K / QK);
+      B.j[u].xd = xd ? xd + (size_t)ic * W.k : nullptr;
+      B.j[u].xqs = xqs + (size_t)ic * nb * 16;
+      B.j[u].xdd = xdd + (size_t)ic * nb;
       B.j[u].bias = bias;
-      B.j[u].y = y + (size_t)ic * M;
+      B.j[u].y = y + (size_t)ic * W.rows;
     }
     if (int rc = launch_gemv_batch(B, mode, s)) return rc;
   }
   return VSIM_OK;
+}
+
+// The general dispatch (vsim_op_q4_gemv, the graph executor): a prompt batch's product on Q4
+// rows, as product_plan has it
+int launch_q4_gemv(const void *w, int M, int K, const void *xq, const float *xd, int n, const float *bias, float *y,
+                   int mode, hipStream_t s) {
+  if (K % QK || M <= 0 || n <= 0) { set_error("q4_gemv: bad shape"); return VSIM_EINVAL; }
+  const W4 W = w4_view(w, M, K);
+  if (mode == VSIM_MODE_EXACT && !xd) { set_error("q4_gemv: exact mode needs xd"); return VSIM_EINVAL; }
+  switch (product_plan({.kind = BatchKind::PROMPT, .mode = mode, .N = n, .M = M, .K = K}).kernel) {
+    case ProductKernel::GEMM_F16: return launch_gemm_q4_f16(W, xq, n, bias, y, s);
+    case ProductKernel::GEMM_EXACT: return launch_gemm_exact(W, xd, n, bias, y, s);
+    case ProductKernel::GEMV_CHAIN: return launch_gemv_rows(W, xq, xd, n, GEMV_JOBS, bias, y, mode, s);
+    case ProductKernel::GEMV_FAST: return launch_gemv_rows(W, xq, xd, n, 1, bias, y, mode, s);
+    default: set_error("q4_gemv: no kernel for this product"); return VSIM_EINVAL;
+  }
 }
 
 // ------------------------------------------------------------------ get_rows
