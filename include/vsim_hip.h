@@ -237,6 +237,18 @@ typedef struct {
   float *oxd;               /* [B][H d] its factors d*(q-8), pair-interleaved as vsim_op_q4_quantize's */
 } vsim_attn_batch_args;
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream);
+/* The same single-query attention for one row (a->B == 1) as the fused layer tail runs it: the
+ * head role of k_layer_tail alone (704 threads per workgroup, write-through output stores, each
+ * head over nsplit = 1 or 2 workgroups that halve its KQV columns), with neither an fc_out nor an
+ * out-projection job in the launch.  The call brings its own head-flag buffer and epoch word and
+ * fails with VSIM_EHIP if a head part did not raise its flag.  Arguments, outputs and bits are
+ * those of vsim_op_attn_decode_batch with B = 1.  The shape must fit the fused kernel: d % 32 == 0,
+ * d <= 256, (d / nsplit) % 32 == 0, H * nsplit <= 128, and q, k, the n_ctx scores and two V tiles
+ * within the kernel's LDS (the model's executor fuses only up to 75264 bytes of them, n_ctx + 2 d
+ * <= 2432; the kernel itself takes more, so this entry also reaches n_ctx = 2048 at d = 256);
+ * else VSIM_EINVAL.
+ * Unlike the batch entry this one waits for the stream before it returns. */
+int vsim_op_tail_attn(const vsim_attn_batch_args *a, int nsplit, void *stream);
 /* Long-prompt GEMM pieces (fast mode, N >= 256 inside the model): the fp16 image [M][K] of a
  * W4T32 weight (values d*(q-8) rounded to fp16), and Y[n][m] (+bias[m]) = sum_k W16[m][k] *
  * X16[n][k] on the 256 x 256-tile fp16 MFMA GEMM (K % 64 == 0; X16 [n][K] fp16). */

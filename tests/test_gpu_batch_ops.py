@@ -11,6 +11,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+import attn_edges as A  # noqa: E402
 from vsim_amd import hip  # noqa: E402
 from vsim_amd import modelgen as mg  # noqa: E402
 
@@ -98,52 +99,10 @@ def test_gemm_rows_argument_errors():
 N_CTX = 512
 
 
-def _kqv_runs(V, p, d, H, nth):
-    """ggml.c:4535-4581 + 4469-4493 for one query: pool thread t mads keys [t dc, t dc + dc) in
-    order in float32 from 0, FINALIZE adds the partial rows in thread order (empty ones as +0).
-    V [nk][H d], p [H][nk] -> [H][d]."""
-    nk = V.shape[0]
-    Vr = V.reshape(nk, H, d)
-    dc = (nk + nth - 1) // nth
-    out = None
-    for t in range(nth):
-        part = np.zeros((H, d), np.float32)
-        for ic in range(dc * t, min(dc * t + dc, nk)):
-            part = (part + (Vr[ic] * p[:, ic:ic + 1]).astype(np.float32)).astype(np.float32)
-        out = part if out is None else (out + part).astype(np.float32)
-    return out
-
-
-def _slopes(H):
-    """ggml_alibi's head slopes, read off the oracle: alibi of a zero score in row 0 is 1 * m_h."""
-    import oracle_py as O
-    z = np.zeros(H, np.float32)
-    O.lib().vo_alibi_f32(O.p(z), 1, 1, H, H)
-    return z
-
-
-def _reference_row(style, q, k, v, kc, vc, pos, d, H, n_rot, scale, alibi, nth):
-    """One sequence's step from the oracle's ops: (out [E], its Q4_0 AoS blocks, the K and V cache
-    rows it writes)."""
-    import oracle_py as O
-    E = d * H
-    if n_rot:
-        name = "neox" if style == 0 else "gptj"
-        q = O.rope(name, q, d, H, 1, pos, n_rot, 0)
-        k = O.rope(name, k, d, H, 1, pos, n_rot, 0)
-    nk, scale = pos + 1, float(scale)
-    K = np.concatenate([kc[:pos], k.reshape(1, E)]).astype(np.float32)
-    V = np.concatenate([vc[:pos], v.reshape(1, E)]).astype(np.float32)
-    s = O.kq(K, q, d, H, nk, 1)
-    if alibi:
-        p = O.attn_softmax_alibi(s, nk, 1, H, pos, H, scale)
-    else:
-        p = O.attn_softmax(s, nk, 1, H, pos, scale)
-    if nth == 1:
-        out = O.kqv(V, p, d, H, nk, 1).reshape(E)
-    else:
-        out = _kqv_runs(V, p.reshape(H, nk), d, H, nth).reshape(E)
-    return out, O.quantize(out), k.reshape(E), v.reshape(E)
+def _reference_row(style, q, k, v, kc, vc, pos, d, H, n_rot, alibi, nth):
+    """One sequence's step from the oracle's ops (tests/attn_edges.py reference_row): (out [E], its
+    Q4_0 AoS blocks, the K and V cache rows it writes)."""
+    return A.reference_row((style, d, H, n_rot, alibi, nth), (q, k, v, kc, vc, pos))
 
 
 def _launch(style, q, k, v, kcs, vcs, pos, d, H, n_rot, scale, slopes, nth, cs):
@@ -173,8 +132,8 @@ CASES = [(0, 64, 2, 32, False, 1), (0, 96, 3, 24, False, 3), (0, 256, 3, 64, Fal
 def test_attn_decode_batch_vs_oracle(style, d, H, n_rot, alibi, nth):
     E, kt = d * H, 8192 // d  # kt: keys per V tile (ATT_VTF / d)
     rng = np.random.default_rng(1000 * d + 10 * H + n_rot + nth)
-    scale = float(np.float32(1.0 / np.sqrt(np.float64(np.float32(d)))))
-    slopes_h = _slopes(H) if alibi else None
+    scale = float(A.head_scale(d))
+    slopes_h = A.slopes(H) if alibi else None
     slopes = dev(slopes_h) if alibi else None
     cs = None  # the RoPE table is the library's own (vsim_op_rope's, checked against the reference)
     # positions at the kernel's seams: first key, the four-keys-per-wave step, the V tile, deep
@@ -191,7 +150,7 @@ def test_attn_decode_batch_vs_oracle(style, d, H, n_rot, alibi, nth):
         out, aos, oq, oxd = _launch(style, qd, kd, vd, kcs, vcs, pos, d, H, n_rot, scale, slopes, nth, cs)
         for b in range(B):
             r_out, r_aos, r_k, r_v = _reference_row(style, q[b], k[b], v[b], kc_h[b], vc_h[b], pos[b], d, H, n_rot,
-                                                    np.float32(scale), alibi, nth)
+                                                    alibi, nth)
             assert np.array_equal(bits(out[b]), bits(r_out)), (pos[b], "out")
             assert np.array_equal(aos[b], r_aos), (pos[b], "Q4 row")
             assert np.array_equal(bits(host(kcs[b])[pos[b]]), bits(r_k)), (pos[b], "K cache row")

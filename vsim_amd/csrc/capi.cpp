@@ -116,6 +116,81 @@ int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
   const AttnRows R{a->kc, a->vc, 0, a->n_past};
   return launch_attn_decode_batch(A, R, a->B, a->n_ctx, (hipStream_t)stream);
 }
+// The heads of k_layer_tail alone (attn_body<704, true>: 11 waves, write-through stores, nsplit
+// workgroups per head): launch_layer_tail with neither an fc_out nor an out-projection job, so
+// every workgroup takes the head role, on a flag buffer and an epoch word of the call's own.
+int vsim_op_tail_attn(const vsim_attn_batch_args *a, int nsplit, void *stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->B != 1 ||
+      a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || nsplit < 1 ||
+      nsplit > 2 || (long long)a->H * nsplit > TAIL_MAX_HEADS) {
+    set_error("tail_attn: bad argument (one row, nsplit 1 or 2, at most 128 head parts)");
+    return VSIM_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DevTables tab;
+  RC(tables_get(&tab));
+  const int half = a->n_rot / 2, na = a->H * nsplit;
+  // one allocation: the epoch word, the heads' flags (8-byte granules), the RoPE table if built here
+  const size_t cs_off = 256 + (size_t)TAIL_MAX_HEADS * sizeof(unsigned long long);
+  const size_t cs_n = a->cs ? 0 : (size_t)a->n_ctx * half;
+  uint8_t *buf = nullptr;
+  VSIM_HIP(hipMalloc(&buf, cs_off + cs_n * sizeof(double2)));
+  unsigned *ep = (unsigned *)buf;
+  unsigned long long *hflag = (unsigned long long *)(buf + 256);
+  std::vector<double2> cs(cs_n);
+  if (cs_n) rope_table_host(cs.data(), a->n_ctx, a->n_rot);
+  const unsigned epoch = 1;
+  float *kc = nullptr, *vc = nullptr;
+  std::vector<unsigned long long> flags(na);
+  int rc = VSIM_EHIP;
+  if (hipMemsetAsync(buf, 0, cs_off, s) == hipSuccess &&
+      hipMemcpyAsync(ep, &epoch, sizeof(epoch), hipMemcpyHostToDevice, s) == hipSuccess &&
+      (!cs_n || hipMemcpyAsync(buf + cs_off, cs.data(), cs_n * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess) &&
+      hipMemcpyAsync(&kc, a->kc, sizeof(kc), hipMemcpyDeviceToHost, s) == hipSuccess &&
+      hipMemcpyAsync(&vc, a->vc, sizeof(vc), hipMemcpyDeviceToHost, s) == hipSuccess &&
+      hipStreamSynchronize(s) == hipSuccess) {
+    const size_t nblk = (size_t)(a->d * a->H / QK);
+    AttnJob A{};
+    A.q = a->q;
+    A.k = a->k;
+    A.v = a->v;
+    A.kc = kc;
+    A.vc = vc;
+    A.npast = a->n_past;
+    A.cs = a->cs ? (const double2 *)a->cs : (const double2 *)(buf + cs_off);
+    A.etab = tab.exp_f16;
+    A.d = a->d;
+    A.H = a->H;
+    A.n_rot = a->n_rot;
+    A.style = a->style;
+    A.n_ctx = a->n_ctx;
+    A.nsplit = nsplit;
+    A.kqv_nth = a->kqv_nth;
+    A.scale = a->scale;
+    A.alibi = a->alibi;
+    A.oq_qs = (uint8_t *)a->oq;
+    A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
+    A.oxd = a->oxd;
+    A.out = a->out;
+    const GemvBatch none{};
+    rc = kc && vc ? launch_layer_tail(none, none, A, TailSync{hflag, ep, 0}, a->n_ctx, s) : VSIM_EINVAL;
+    if (rc == VSIM_OK) {
+      // every head part must have raised its flag with this call's tag (epoch << 8 | layer + 1)
+      if (hipMemcpyAsync(flags.data(), hflag, na * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
+          hipStreamSynchronize(s) != hipSuccess) {
+        rc = VSIM_EHIP;
+      } else {
+        for (int i = 0; i < na; ++i)
+          if ((unsigned)(flags[i] >> 32) != ((epoch << 8) | 1u)) {
+            set_error("tail_attn: a head part did not raise its flag");
+            rc = VSIM_EHIP;
+          }
+      }
+    }
+  }
+  (void)hipFree(buf);
+  return rc;
+}
 int vsim_op_q4_expand_f16(const void *w, int M, int K, void *w16, void *stream) {
   if (!w || !w16 || M <= 0 || K <= 0 || K % QK) { set_error("q4_expand_f16: bad argument"); return VSIM_EINVAL; }
   return launch_w4_expand_f16(w4_view(w, M, K), w16, (hipStream_t)stream);

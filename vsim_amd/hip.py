@@ -55,6 +55,7 @@ EXPORTS = [
     "vsim_op_attn_prefill_layout", "vsim_op_attn_prefill_scratch", "vsim_op_gemm_q4_256_h16",
     "vsim_op_gemm_q4_256_pair_h16",
     "vsim_op_topk_rows", "vsim_topk_rows_set_wg", "vsim_model_decode_batch_sample", "vsim_model_seq_copy",
+    "vsim_op_tail_attn",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -289,6 +290,7 @@ def lib():
     L.vsim_op_q4_gemm_rows.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.vsim_batch_set_gemm.argtypes = [ci]
     L.vsim_op_attn_decode_batch.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
+    L.vsim_op_tail_attn.argtypes = [ctypes.POINTER(AttnBatchArgs), ci, vp]
     L.vsim_model_seq_reserve.argtypes = [vp, ci]
     L.vsim_model_eval_seq.argtypes = [vp, ci, ci, vp, ci, vp]
     L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
@@ -469,6 +471,15 @@ def attn_decode_batch(q, k, v, kc, vc, n_past, cs, alibi, B, d, H, n_rot, style,
     a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), B, d, H, n_rot,
                       style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
     check(lib().vsim_op_attn_decode_batch(ctypes.byref(a), stream), "attn_decode_batch")
+
+
+def tail_attn(q, k, v, kc, vc, n_past, cs, alibi, d, H, n_rot, style, n_ctx, kqv_nth, scale, out, oq, oxd, nsplit,
+              stream=None):
+    """vsim_op_tail_attn: one row of attn_decode_batch's operands (kc, vc int64 tensors [1]) through
+    the fused layer tail's head role, each head over nsplit (1 or 2) workgroups."""
+    a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), 1, d, H, n_rot,
+                      style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
+    check(lib().vsim_op_tail_attn(ctypes.byref(a), int(nsplit), stream), "tail_attn")
 
 
 def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,

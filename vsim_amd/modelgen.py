@@ -111,6 +111,8 @@ CONFIGS = {
     "small-neox": ("gptneox", HParams(512, 512, 8, 2, 32)),
     "tiny-gptj": ("gptj", HParams(128, 128, 4, 2, 16)),
     "small-gptj": ("gptj", HParams(512, 512, 4, 2, 64)),
+    # GPT-J-6B's head dim (d = 256) at E = 512: the context-length seam of the fused layer tail
+    "seam-gptj": ("gptj", HParams(512, 512, 2, 2, 64)),
     # BLOOM (ALiBi, no rotary: n_rot 0; serial residual; header n_mult = 1)
     "bloom-560m": ("bloom", HParams(250880, 1024, 16, 24, 0, 0)),
     "tiny-bloom": ("bloom", HParams(128, 128, 4, 2, 0, 0)),
