@@ -249,6 +249,56 @@ int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream);
  * else VSIM_EINVAL.
  * Unlike the batch entry this one waits for the stream before it returns. */
 int vsim_op_tail_attn(const vsim_attn_batch_args *a, int nsplit, void *stream);
+/* The whole fused layer tail with the next LayerNorm in it (k_layer_tail with its TailLn, what every
+ * exact decode step of the parallel-residual graphs runs once per layer), on the call's operands:
+ *   heads   the single-query attention of `attn` (B == 1), each head over nsplit workgroups; its Q4
+ *           row attn.oq / attn.oxd (and attn.out) are outputs of this call as well;
+ *   a       = wo . that row            (W4T32 [E][E], E = d H; the exact chain of vsim_op_q4_gemv)
+ *   f       = wf . xd                  (W4T32 [E][K]; xd [K] the factors of vsim_op_q4_quantize)
+ *   v[i]    = x[i] + ((a[i] + ab[i]) + (f[i] + fb[i]))   in float32 (ab NULL: a[i] alone) -> jout
+ *   y       = ggml_compute_forward_norm_f32 of v (mean and sum of squares summed in order in double,
+ *             scale (float)(1/sqrt(s2/E + 1e-5f)), y = (float)(v - mean) * scale)
+ *   z1      = w1 * y + b1  (two float roundings), quantize_row_q4_0 -> q1 (Q4 SoA: nibbles [E/32][16],
+ *             then scales [E/32]) and its factors xd1 [E], as vsim_op_q4_quantize's of z1;
+ *   z2      likewise from the same y with w2, b2 into q2, xd2 when all four are given (none: one norm).
+ * Bit for bit the reference's values; how the kernel gets there (per-tile partial sums, the mean and
+ * moments certificates, the sequential fallbacks) shows only in vsim_norm_fallbacks: a launch adds at
+ * most one to each counter ([0] the mean was not certified, [1] the fallback's scale interval was
+ * ambiguous and the sum of squares was redone in order).
+ * Hand-offs inside the launch are tagged epoch << 8 | il + 1 (il = 0..254).  ws NULL: the call brings
+ * a zeroed workspace of its own.  ws given (vsim_op_tail_ln_ws_bytes(E) bytes, 256-byte aligned,
+ * zeroed by the caller before its first use): the call writes the epoch word and reuses whatever
+ * granules earlier calls left, which never match as long as the tag differs from the previous
+ * call's on that workspace -- the executor's situation from layer to layer and step to step.
+ * VSIM_EINVAL for what the fused kernel refuses: B != 1, nsplit outside 1..2, d % 32, d > 256,
+ * (d / nsplit) % 32, H nsplit > 128, the LDS bound of vsim_op_tail_attn, K % 32, E/32 not below the
+ * device's CU count (every out-projection tile must be resident at once), il outside 0..254, a
+ * missing operand, an incomplete second norm, a short or misaligned ws.  VSIM_EHIP if a head part
+ * did not raise its flag, VSIM_ESPIN if a bounded wait inside the kernel gave up during the call
+ * (vsim_spin_timeouts grew).  Stream-ordered; waits for the stream before it returns. */
+typedef struct {
+  vsim_attn_batch_args attn; /* the attention row, B == 1 */
+  int32_t nsplit;            /* workgroups per head, 1 or 2 */
+  int32_t K;                 /* fc_out's inner size */
+  const void *wo;            /* out-projection weight, W4T32 [E][E] */
+  const void *wf;            /* fc_out weight, W4T32 [E][K] */
+  const float *xd;           /* [K] fc_out's activation factors */
+  const float *x;            /* [E] residual in */
+  const float *ab, *fb;      /* [E] biases of the two branches (ab may be NULL) */
+  const float *w1, *b1;      /* [E] norm 1 affine */
+  const float *w2, *b2;      /* [E] norm 2 affine, or both NULL */
+  float *jout;               /* [E] the joined row v */
+  void *q1;                  /* norm 1 as Q4 SoA */
+  float *xd1;                /* [E] its factors */
+  void *q2;                  /* norm 2 outputs, or both NULL */
+  float *xd2;
+  uint32_t epoch;            /* the tag: epoch << 8 | il + 1 */
+  int32_t il;
+  void *ws;                  /* optional caller-owned workspace */
+  size_t ws_bytes;
+} vsim_tail_ln_args;
+size_t vsim_op_tail_ln_ws_bytes(int E); /* 0 for an E that is no positive multiple of 32 */
+int vsim_op_tail_ln(const vsim_tail_ln_args *a, void *stream);
 /* Long-prompt GEMM pieces (fast mode, N >= 256 inside the model): the fp16 image [M][K] of a
  * W4T32 weight (values d*(q-8) rounded to fp16), and Y[n][m] (+bias[m]) = sum_k W16[m][k] *
  * X16[n][k] on the 256 x 256-tile fp16 MFMA GEMM (K % 64 == 0; X16 [n][K] fp16). */

@@ -135,6 +135,23 @@ def test_fp16_tables_match_reference():
     assert np.array_equal(g, g_ref)
 
 
+def test_ctypes_tail_ln_args_layout():
+    """vsim_amd.hip.TailLnArgs and AttnBatchArgs have the layout a C compiler gives
+    vsim_tail_ln_args and vsim_attn_batch_args (include/vsim_hip.h)."""
+    import ctypes
+    structs = {"vsim_tail_ln_args": hip.TailLnArgs, "vsim_attn_batch_args": hip.AttnBatchArgs}
+    lines = []
+    for cname, cls in structs.items():
+        lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]
+        lines.append(f'printf("{cname}.sizeof %zu\\n", sizeof({cname}));')
+    src = '#include <stddef.h>\n#include <stdio.h>\n#include "vsim_hip.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n"
+    want = dict(ln.split() for ln in _run_c(src, os.path.join(ROOT, "include")).splitlines())
+    for cname, cls in structs.items():
+        for f, _ in cls._fields_:
+            assert getattr(cls, f).offset == int(want[f"{cname}.{f}"]), (cname, f)
+        assert ctypes.sizeof(cls) == int(want[f"{cname}.sizeof"]), cname
+
+
 def test_ctypes_ggml_mirror_layout():
     """vsim_amd.hip.GgmlTensor (the Python callers' mirror) has include/ggml_abi.h's layout."""
     mine = _run_c(_offsets_program('#include "ggml_abi.h"'), os.path.join(ROOT, "include"))

@@ -191,6 +191,155 @@ int vsim_op_tail_attn(const vsim_attn_batch_args *a, int nsplit, void *stream) {
   (void)hipFree(buf);
   return rc;
 }
+// The whole k_layer_tail with its LayerNorm (TailJob::ln): launch_layer_tail(Bf, Bo, A, sy, n_ctx, s, &N)
+// on the call's operands.  Workspace (the caller's, or one of the call's own, zeroed): the epoch
+// word (own 256-byte line), og [E], jg [E], rec [2 E/32], the heads' flags -- the executor's block.
+static size_t tail_ln_ws_bytes(size_t E) {
+  return 256 + 2 * E * sizeof(unsigned long long) + 2 * (E / QK) * sizeof(uint4) +
+         (size_t)TAIL_MAX_HEADS * sizeof(unsigned long long);
+}
+size_t vsim_op_tail_ln_ws_bytes(int E) { return E > 0 && E % QK == 0 ? tail_ln_ws_bytes((size_t)E) : 0; }
+int vsim_op_tail_ln(const vsim_tail_ln_args *t, void *stream) {
+  const vsim_attn_batch_args *a = t ? &t->attn : nullptr;
+  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->B != 1 ||
+      a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || t->nsplit < 1 ||
+      t->nsplit > 2 || (long long)a->H * t->nsplit > TAIL_MAX_HEADS || (long long)a->d * a->H > LNT_MAX_TILES * T32 ||
+      a->d % QK || a->d > 256 || a->d % t->nsplit || (a->d / t->nsplit) % QK) {
+    set_error("tail_ln: bad attention row (one row, d % 32 == 0, d <= 256, nsplit 1 or 2 with whole 32-blocks per "
+              "part, at most 128 head parts, E <= 8192)");
+    return VSIM_EINVAL;
+  }
+  const int E = a->d * a->H;
+  if (E % QK || !t->wo || !t->wf || !t->xd || t->K <= 0 || t->K % QK || !t->x || !t->fb || !t->w1 || !t->b1 ||
+      !t->jout || !t->q1 || !t->xd1) {
+    set_error("tail_ln: wo, wf, xd (K a multiple of 32), x, fb, w1, b1, jout, q1 and xd1 are required");
+    return VSIM_EINVAL;
+  }
+  const bool two = t->w2 || t->b2 || t->q2 || t->xd2;
+  if (two && (!t->w2 || !t->b2 || !t->q2 || !t->xd2)) {
+    set_error("tail_ln: the second norm needs w2, b2, q2 and xd2");
+    return VSIM_EINVAL;
+  }
+  if (t->il < 0 || t->il > 254) {
+    set_error("tail_ln: the layer index of the tag is 0..254");
+    return VSIM_EINVAL;
+  }
+  if (t->ws && (t->ws_bytes < tail_ln_ws_bytes(E) || ((uintptr_t)t->ws & 255))) {
+    set_error("tail_ln: the workspace is vsim_op_tail_ln_ws_bytes(E) bytes, 256-byte aligned");
+    return VSIM_EINVAL;
+  }
+  if (!tail_ln_ok(E)) {
+    set_error("tail_ln: E/32 must stay below the CU count (every out-projection tile resident at once)");
+    return VSIM_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  DevTables tab;
+  RC(tables_get(&tab));
+  const int half = a->n_rot / 2, na = a->H * t->nsplit;
+  // one allocation of the call's own: the workspace unless the caller brought one, the RoPE table if built here
+  const size_t ws_n = t->ws ? 0 : tail_ln_ws_bytes(E);
+  const size_t cs_n = a->cs ? 0 : (size_t)a->n_ctx * half;
+  uint8_t *buf = nullptr;
+  if (ws_n + cs_n) VSIM_HIP(hipMalloc(&buf, ws_n + cs_n * sizeof(double2)));
+  uint8_t *ws = t->ws ? (uint8_t *)t->ws : buf;
+  unsigned *ep = (unsigned *)ws;
+  unsigned long long *og = (unsigned long long *)(ws + 256), *jg = og + E;
+  uint4 *rec = (uint4 *)(jg + E);
+  unsigned long long *hflag = (unsigned long long *)(rec + 2 * (E / QK));
+  std::vector<double2> cs(cs_n);
+  if (cs_n) rope_table_host(cs.data(), a->n_ctx, a->n_rot);
+  const unsigned epoch = t->epoch, tag = (epoch << 8) | (unsigned)(t->il + 1);
+  unsigned *spin = spin_error_counter();
+  unsigned spin0 = 0, spin1 = 0;
+  float *kc = nullptr, *vc = nullptr;
+  std::vector<unsigned long long> flags(na);
+  int rc = VSIM_EHIP;
+  if ((!ws_n || hipMemsetAsync(buf, 0, ws_n, s) == hipSuccess) &&
+      hipMemcpyAsync(ep, &epoch, sizeof(epoch), hipMemcpyHostToDevice, s) == hipSuccess &&
+      (!cs_n || hipMemcpyAsync(buf + ws_n, cs.data(), cs_n * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess) &&
+      hipMemcpyAsync(&kc, a->kc, sizeof(kc), hipMemcpyDeviceToHost, s) == hipSuccess &&
+      hipMemcpyAsync(&vc, a->vc, sizeof(vc), hipMemcpyDeviceToHost, s) == hipSuccess &&
+      (!spin || hipMemcpyAsync(&spin0, spin, sizeof(spin0), hipMemcpyDeviceToHost, s) == hipSuccess) &&
+      hipStreamSynchronize(s) == hipSuccess) {
+    const size_t nblk = (size_t)(E / QK);
+    AttnJob A{};
+    A.q = a->q;
+    A.k = a->k;
+    A.v = a->v;
+    A.kc = kc;
+    A.vc = vc;
+    A.npast = a->n_past;
+    A.cs = a->cs ? (const double2 *)a->cs : (const double2 *)(buf + ws_n);
+    A.etab = tab.exp_f16;
+    A.d = a->d;
+    A.H = a->H;
+    A.n_rot = a->n_rot;
+    A.style = a->style;
+    A.n_ctx = a->n_ctx;
+    A.nsplit = t->nsplit;
+    A.kqv_nth = a->kqv_nth;
+    A.scale = a->scale;
+    A.alibi = a->alibi;
+    A.oq_qs = (uint8_t *)a->oq;
+    A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
+    A.oxd = a->oxd;
+    A.out = a->out;
+    GemvBatch Bf{}, Bo{};
+    Bf.nj = Bo.nj = 1;
+    Bf.j[0].w = w4_view(t->wf, E, t->K);  // fc_out on the caller's factors
+    Bf.j[0].xd = t->xd;
+    Bf.j[0].epi = EPI_STORE;
+    Bo.j[0].w = w4_view(t->wo, E, E);  // the out-projection on the heads' output
+    Bo.j[0].xd = a->oxd;
+    Bo.j[0].xqs = A.oq_qs;
+    Bo.j[0].xdd = A.oq_d;
+    Bo.j[0].epi = EPI_STORE;
+    TailLn N{};
+    N.x = t->x;
+    N.ab = t->ab;
+    N.fb = t->fb;
+    N.jout = t->jout;
+    N.w1 = t->w1;
+    N.b1 = t->b1;
+    N.q1 = (uint8_t *)t->q1;
+    N.d1 = (float *)((uint8_t *)t->q1 + nblk * 16);
+    N.xd1 = t->xd1;
+    if (two) {
+      N.w2 = t->w2;
+      N.b2 = t->b2;
+      N.q2 = (uint8_t *)t->q2;
+      N.d2 = (float *)((uint8_t *)t->q2 + nblk * 16);
+      N.xd2 = t->xd2;
+    }
+    N.og = og;
+    N.jg = jg;
+    N.rec = rec;
+    N.ep = ep;
+    N.stats = dev_stats();
+    N.il = t->il;
+    rc = kc && vc ? launch_layer_tail(Bf, Bo, A, TailSync{hflag, ep, t->il}, a->n_ctx, s, &N) : VSIM_EINVAL;
+    if (rc == VSIM_OK) {
+      // every head part must have raised its flag with this call's tag, and no bounded wait may have given up
+      if (hipMemcpyAsync(flags.data(), hflag, na * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
+          (spin && hipMemcpyAsync(&spin1, spin, sizeof(spin1), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+          hipStreamSynchronize(s) != hipSuccess) {
+        rc = VSIM_EHIP;
+      } else {
+        for (int i = 0; i < na; ++i)
+          if ((unsigned)(flags[i] >> 32) != tag) {
+            set_error("tail_ln: a head part did not raise its flag");
+            rc = VSIM_EHIP;
+          }
+        if (spin1 != spin0) {
+          set_error("tail_ln: a bounded wait inside the layer tail gave up");
+          rc = VSIM_ESPIN;
+        }
+      }
+    }
+  }
+  if (buf) (void)hipFree(buf);
+  return rc;
+}
 int vsim_op_q4_expand_f16(const void *w, int M, int K, void *w16, void *stream) {
   if (!w || !w16 || M <= 0 || K <= 0 || K % QK) { set_error("q4_expand_f16: bad argument"); return VSIM_EINVAL; }
   return launch_w4_expand_f16(w4_view(w, M, K), w16, (hipStream_t)stream);

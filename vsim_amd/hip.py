@@ -55,7 +55,7 @@ EXPORTS = [
     "vsim_op_attn_prefill_layout", "vsim_op_attn_prefill_scratch", "vsim_op_gemm_q4_256_h16",
     "vsim_op_gemm_q4_256_pair_h16",
     "vsim_op_topk_rows", "vsim_topk_rows_set_wg", "vsim_model_decode_batch_sample", "vsim_model_seq_copy",
-    "vsim_op_tail_attn",
+    "vsim_op_tail_attn", "vsim_op_tail_ln", "vsim_op_tail_ln_ws_bytes",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -165,6 +165,16 @@ class AttnBatchArgs(ctypes.Structure):
                 ("n_rot", ctypes.c_int32), ("style", ctypes.c_int32), ("n_ctx", ctypes.c_int32),
                 ("kqv_nth", ctypes.c_int32), ("scale", ctypes.c_float), ("out", ctypes.c_void_p),
                 ("oq", ctypes.c_void_p), ("oxd", ctypes.c_void_p)]
+
+
+class TailLnArgs(ctypes.Structure):
+    """vsim_tail_ln_args (include/vsim_hip.h)."""
+    _fields_ = [("attn", AttnBatchArgs), ("nsplit", ctypes.c_int32), ("K", ctypes.c_int32), ("wo", ctypes.c_void_p),
+                ("wf", ctypes.c_void_p), ("xd", ctypes.c_void_p), ("x", ctypes.c_void_p), ("ab", ctypes.c_void_p),
+                ("fb", ctypes.c_void_p), ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w2", ctypes.c_void_p),
+                ("b2", ctypes.c_void_p), ("jout", ctypes.c_void_p), ("q1", ctypes.c_void_p), ("xd1", ctypes.c_void_p),
+                ("q2", ctypes.c_void_p), ("xd2", ctypes.c_void_p), ("epoch", ctypes.c_uint32), ("il", ctypes.c_int32),
+                ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t)]
 
 
 class QuantizeStats(ctypes.Structure):
@@ -291,6 +301,9 @@ def lib():
     L.vsim_batch_set_gemm.argtypes = [ci]
     L.vsim_op_attn_decode_batch.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
     L.vsim_op_tail_attn.argtypes = [ctypes.POINTER(AttnBatchArgs), ci, vp]
+    L.vsim_op_tail_ln.argtypes = [ctypes.POINTER(TailLnArgs), vp]
+    L.vsim_op_tail_ln_ws_bytes.restype = sz
+    L.vsim_op_tail_ln_ws_bytes.argtypes = [ci]
     L.vsim_model_seq_reserve.argtypes = [vp, ci]
     L.vsim_model_eval_seq.argtypes = [vp, ci, ci, vp, ci, vp]
     L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
@@ -480,6 +493,25 @@ def tail_attn(q, k, v, kc, vc, n_past, cs, alibi, d, H, n_rot, style, n_ctx, kqv
     a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), 1, d, H, n_rot,
                       style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
     check(lib().vsim_op_tail_attn(ctypes.byref(a), int(nsplit), stream), "tail_attn")
+
+
+def tail_ln_ws_bytes(E: int) -> int:
+    """Bytes of a caller-owned tail_ln workspace for width E (zero it before its first use)."""
+    return int(lib().vsim_op_tail_ln_ws_bytes(int(E)))
+
+
+def tail_ln_args(attn, nsplit, wo, wf, xd, K, x, ab, fb, w1, b1, w2, b2, jout, q1, xd1, q2, xd2, epoch, il, ws=None):
+    """vsim_tail_ln_args from an AttnBatchArgs (B = 1) and torch tensors (or None)."""
+    nws = 0 if ws is None else int(ws.numel() * ws.element_size())
+    return TailLnArgs(attn, int(nsplit), int(K), ptr(wo), ptr(wf), ptr(xd), ptr(x), ptr(ab), ptr(fb), ptr(w1), ptr(b1),
+                      ptr(w2), ptr(b2), ptr(jout), ptr(q1), ptr(xd1), ptr(q2), ptr(xd2), int(epoch), int(il), ptr(ws),
+                      nws)
+
+
+def tail_ln(args, stream=None):
+    """vsim_op_tail_ln: the fused layer tail with its LayerNorm on the operands of `args`
+    (tail_ln_args); waits for the stream."""
+    check(lib().vsim_op_tail_ln(ctypes.byref(args), stream), "tail_ln")
 
 
 def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,
