@@ -58,6 +58,9 @@ extern "C" {
 /* numeric modes */
 #define VSIM_MODE_EXACT 0 /* bit-identical to the reference at --threads 1            */
 #define VSIM_MODE_FAST 1  /* split-K integer-dot GEMV: same math, different rounding  */
+#define VSIM_MODE_W4A16 2 /* weight-only: Q4_0 weights, activation rows rounded to fp16 (not
+                             quantized), fp32 accumulation -- not the reference's arithmetic;
+                             see vsim_op_q4_gemm_w4a16_rows and vsim_model_set_mode          */
 
 /* architectures */
 #define VSIM_ARCH_GPTNEOX 0 /* vsim.cpp:470-747                                      */
@@ -203,6 +206,50 @@ int vsim_batch_set_gemm(int enable);
  * or y.  Enqueued on stream, not synchronized. */
 int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n, const float *bias, float *y,
                               void *stream);
+/* ---- weight-only mode (VSIM_MODE_W4A16): the row operand and the product (gemm_w4a16_rows.hip).
+ * Every product of the mode is these two kernels; everything that is not a product stays the exact
+ * path's kernel.
+ *
+ * Row operand (k_w4a16_rows).  For each of n rows x[K] (f32), on its own:
+ *   amax = the largest |x[i]| among the row's finite elements (f32 subnormals count as they are);
+ *   e    = 14 - floor(log2(amax)): the integer that puts amax * 2^e into [2^14, 2^15); e = 0 for
+ *          an all-zero row (-0.0 is zero);
+ *   h[i] = fp16_rn(x[i] * 2^e): the scaling is exact, the conversion rounds to nearest even; no
+ *          finite row overflows fp16.  Elements more than 2^28 or so below amax become fp16
+ *          subnormals (kept as such in x16, multiples of 2^-24) or signed zeros.
+ * Subnormal rule: gfx950's v_mfma_f32_16x16x32_f16 takes fp16 subnormal A / B inputs at their value
+ * (it does not flush them; measured, tests/test_gpu_w4a16_ops.py), so the product below uses every h
+ * as stored.
+ * Non-finite rule: a row that holds a NaN or an Inf gets e = VSIM_W4A16_NONFINITE and h = +0
+ * throughout, and every output of that row is the quiet NaN 0x7FC00000.  No other row is touched.
+ * x16 [n][K] halves (16-byte aligned), e [n]; x at any 4-byte alignment (16-byte aligned rows of up
+ * to 16,384 elements take a faster form of the kernel, same bits).  One launch per distinct operand: Q, K and V share
+ * theirs.
+ *
+ * Product (k_gemm_w4a16_rows): y[n][M] for n = 1 .. VSIM_BATCH_MAX rows against a W4T32 weight, every
+ * weight block fetched and unpacked once per workgroup (16 weight rows) for all n rows.  Per
+ * (weight row, activation row), with nb = K / 32:
+ *   dot_b   = the matrix core's sum, from C = 0, of block b's 32 products (q - 8) * h (each exact
+ *             in fp32; the order of the 32 adds is the instruction's, fixed);
+ *   part[p] = 0.0f; for b = p, p + 16, p + 32, ... < nb:
+ *               part[p] = fmaf(d_w[b], dot_b, part[p])          (p = 0 .. 15; no block: stays +0);
+ *   sum     = 0.0f; for p = 0 .. 15: sum += part[p];
+ *   s       = sum * 2^-e                (exact, unless s is an f32 subnormal: then rounded once);
+ *   y       = bias ? s + bias[row] : s.
+ * Contract (a), row independence, bit for bit: output (j, m) depends on activation row j and weight
+ * row m only -- not on n, on j's index in the launch or on the other rows.
+ * Contract (b): against the same formula evaluated in double on the same h,
+ *   |y - y64| <= c(K) 2^-24 sum_b |d_w[b]| sum_i |q_i - 8| |h_i| 2^-e  (+ the bias add's rounding,
+ *   + 2^-149 where s is subnormal),  c(K) = 32 + ceil(nb / 16) + 16 + 1
+ * (32 adds inside the MFMA, the partial's fmas, the partial adds, one unit for the second-order
+ * terms: tests/w4a16_ref.py derives it).
+ * Activation rows >= n are not read, y rows >= n not written, nothing behind the weight is read.
+ * VSIM_EINVAL for n outside 1..VSIM_BATCH_MAX, K % 32 != 0, M <= 0 or a NULL w, x, x16, e or y (bias
+ * may be NULL).  Both are enqueued on stream and not synchronized. */
+#define VSIM_W4A16_NONFINITE (-2147483647 - 1)
+int vsim_op_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, void *stream);
+int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, const int32_t *e, int n,
+                               const float *bias, float *y, void *stream);
 /* Process-wide choice of how vsim_op_q4_gemm_fast_rows and the products of
  * vsim_model_decode_batch_fast run: 0: one k_gemv_fast launch per row (the weight streams once per
  * row); 1 (default): k_gemm_fast_rows from the smallest row count where it was measured faster by
@@ -645,7 +692,29 @@ int vsim_model_get_tensor(vsim_model *m, const char *name, void *host, size_t nb
 int vsim_model_randomize(vsim_model *m, uint64_t seed, float std);
 /* VSIM_MODE_FAST on a model whose n_ctx exceeds 4096 (more than 64 chunks of 64 positions, the
  * limit of the fast decode step's attention merge) selects VSIM_MODE_EXACT: every eval of such a
- * model is the exact one, bit for bit. */
+ * model is the exact one, bit for bit.
+ * VSIM_MODE_W4A16 (weight-only: every product is vsim_op_w4a16_rows + vsim_op_q4_gemm_w4a16_rows on
+ * the f32 activation rows; LayerNorm, RoPE, KQ with double sums, the fp16-table softmax, the KQV
+ * float chain, the table GELU, the joins and the embedding rows are the exact path's kernels; the
+ * fast prompt attention, the fp16 GEMMs and their epilogues are not used; one exception, BLOOM's
+ * prompt softmax: the reference adds the ALiBi term (j + 1) m_h to row j of a batch, a per-row
+ * constant that no softmax depends on except in its rounding, and this mode adds the single-token
+ * step's 1 m_h to every row instead, so that a row does not depend on its place in a batch) is
+ * accepted on a whole
+ * model (layers [0, n_layer)) at any n_ctx; VSIM_EINVAL on a pipeline stage.  Every kernel of the
+ * mode is per row, so in this mode, bit for bit:
+ *   - an eval of N tokens leaves the cache rows of N single-token evals, and its logits row is
+ *     theirs (a product of N rows is ceil(N / 32) launches of the rows kernel on consecutive
+ *     32-row chunks: a chunked weight pass, chosen because chunking cannot change a row's bits);
+ *   - row i of vsim_model_eval_score's logits_all is the logits row of the eval ending at i,
+ *     whatever the head's chunk size;
+ *   - row b of vsim_model_decode_batch_w4a16 is vsim_model_eval_seq's row for that sequence alone;
+ *   - switching to another mode and back changes neither mode's bits.
+ * All whole-model entry points work in the mode: vsim_model_eval, _eval_seq and _eval_score on the
+ * general path (N = 1 included), _eval_argmax, _generate, _eval_sample and _generate_sampled as
+ * uncaptured general-path steps on slot 0 with one host round trip per token (no hipGraph in this
+ * mode yet).  The pipeline stage calls (vsim_model_stage_bind / _begin / _step) return VSIM_EINVAL
+ * while the model is in this mode. */
 int vsim_model_set_mode(vsim_model *m, int mode);
 /* Allocates ahead what a prompt of up to n_tokens sets up on its first eval (the N-token
  * scratch, the fp16 key copies of the prompt attention, the GEMMs' stream-K workspace) and
@@ -736,6 +805,18 @@ int vsim_model_decode_batch(vsim_model *m, int B, const int32_t *seq, const int3
 int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
                                  const int32_t *tokens, float *logits /* host [B][n_vocab] or NULL */,
                                  int32_t *next /* host [B] or NULL */);
+/* The same step with weight-only products (VSIM_MODE_W4A16), whatever vsim_model_set_mode says: the
+ * call names its numeric path as vsim_model_decode_batch_fast does.  Arguments, checks and errors are
+ * vsim_model_decode_batch's (without the mode refusal).  Every product runs on the rows' fp16
+ * operand through vsim_op_q4_gemm_w4a16_rows (the attention hands its f32 output row to the
+ * out-projection), the weights stream once per step for all B rows, the other kernels are the exact
+ * step's.  Contract: row b of logits is bit for bit the row vsim_model_eval_seq(m, seq[b],
+ * n_past[b], &tokens[b], 1, logits) gives on this model in VSIM_MODE_W4A16 from the same cache
+ * state, and the cache rows written are the same -- for every B, every mix of positions and every
+ * row order -- so a slot may be advanced by either call. */
+int vsim_model_decode_batch_w4a16(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                  const int32_t *tokens, float *logits /* host [B][n_vocab] or NULL */,
+                                  int32_t *next /* host [B] or NULL */);
 /* The batched step, sampled: vsim_model_decode_batch (mode = VSIM_MODE_EXACT) or
  * vsim_model_decode_batch_fast (VSIM_MODE_FAST) up to the head, then row b's candidate stage with
  * samplers[b]'s window, k, temperature and penalty -- all rows in one k_sample_topk_rows launch
@@ -760,6 +841,16 @@ int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const
 int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
                                    const int32_t *tokens, vsim_sampler *const *samplers /* [B] */,
                                    int32_t *next /* host [B] */);
+/* The sampled batched step with weight-only products: vsim_model_decode_batch_sample's arguments,
+ * checks and device / host sampler paths with vsim_model_decode_batch_w4a16 up to the head, whatever
+ * the model's mode.  Contract: next[b] and samplers[b]'s state afterwards are those of
+ * vsim_model_eval_seq on this model in VSIM_MODE_W4A16, vsim_op_topk on its logits row and
+ * vsim_sampler_pick, on the same cache.  (An entry of its own: vsim_model_decode_batch_sample's mode
+ * argument stays EXACT / FAST, every other value VSIM_EINVAL, as tests/test_gpu_batch_sample_model.py
+ * pins it.) */
+int vsim_model_decode_batch_sample_w4a16(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                         const int32_t *tokens, vsim_sampler *const *samplers /* [B] */,
+                                         int32_t *next /* host [B] */);
 /* Slot fork: cache rows [0, n_tokens) of K and V of every layer go from slot src to slot dst
  * (device to device on the model's stream, one strided copy each; ordered with the steps before
  * and after it, not synchronized).  A slot holds nothing but these rows, so dst then continues

@@ -29,6 +29,13 @@ decode_batch_fast with the [B][n_vocab] logits copied out and vsim_sampler_sampl
 from --baseline-lib in a child process.
 
   python tools/batch_bench.py --sample --out profiles/batch_sample_bench.txt --baseline-lib PATH --tree "..."
+
+--mode w4a16 measures vsim_model_decode_batch_w4a16 (weight-only products: Q4_0 weights, fp16
+activation rows) beside decode_batch_fast and decode_batch of --baseline-lib in child processes, then
+one profiled B = 32 step with the product's weight bytes per second, then one Model.score window of
+--score-tokens tokens (default 2048; 0: none) in the new mode, in fast and in exact mode.
+
+  python tools/batch_bench.py --mode w4a16 --bs 1,4,8,16,32 --out profiles/w4a16_bench.txt --baseline-lib PATH --tree "..."
 """
 import argparse
 import ctypes
@@ -105,6 +112,10 @@ def baseline_child_batch(a, L, h, ck):
     vp, ci = ctypes.c_void_p, ctypes.c_int
     L.vsim_model_seq_reserve.argtypes = [vp, ci]
     L.vsim_model_decode_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    step = L.vsim_model_decode_batch
+    if a.child_mode == "fast":  # (the model is in fast mode: the fast step)
+        step = L.vsim_model_decode_batch_fast
+        step.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     bs = [int(b) for b in a.bs.split(",")]
     ck(L.vsim_model_seq_reserve(h, max(bs)), "seq_reserve")
     n, res = a.pos1 - a.pos0, {}
@@ -116,8 +127,7 @@ def baseline_child_batch(a, L, h, ck):
                 if p == a.pos0:
                     t0 = time.perf_counter()
                 npst = np.full(B, p, np.int32)
-                ck(L.vsim_model_decode_batch(h, B, seqs.ctypes.data, npst.ctypes.data, tok.ctypes.data, None,
-                                             nxt.ctypes.data), "decode_batch")
+                ck(step(h, B, seqs.ctypes.data, npst.ctypes.data, tok.ctypes.data, None, nxt.ctypes.data), "decode_batch")
                 tok = nxt.copy()
             runs.append(B * n / (time.perf_counter() - t0))
         res[B] = {"tok_s": statistics.median(runs), "runs": runs}
@@ -262,12 +272,12 @@ def run_baseline(a, lib, kind="generate", mode="exact"):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
-def timed_steps(dm, B, pos0, pos1, timed=True, fast=False):
+def timed_steps(dm, B, pos0, pos1, timed=True, fast=False, w4a16=False):
     """Positions [0, pos1) of B sequences in slots 0..B-1; returns the seconds of [pos0, pos1)."""
     seqs = list(range(B))
     tok = [3 + b for b in range(B)]
     t0 = 0.0
-    step = dm.decode_batch_fast if fast else dm.decode_batch
+    step = dm.decode_batch_w4a16 if w4a16 else dm.decode_batch_fast if fast else dm.decode_batch
     for p in range(pos1):
         if p == pos0:
             t0 = time.perf_counter()
@@ -355,9 +365,83 @@ def main_fast(a):
             f.write("\n".join(lines) + "\n")
 
 
+def main_w4a16(a):
+    """--mode w4a16: decode_batch_w4a16 beside the baseline library's fast and exact batched steps,
+    where one B = 32 step's time goes, and one scoring window in the three modes."""
+    from vsim_amd import hip
+    import torch
+    arch_s, hp = hparams(a.config, a.layers)
+    bs = [int(b) for b in a.bs.split(",")]
+    n_ctx = a.n_ctx
+    dm = hip.Model.create(ARCH[arch_s], hp, n_ctx=n_ctx)
+    dm.randomize(seed=1, std=0.02)
+    dm.set_mode(hip.MODE_W4A16)
+    dm.seq_reserve(max(bs + [32]))
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    box = f"{socket.gethostname()} {torch.cuda.get_device_properties(0).gcnArchName}"
+    n = a.pos1 - a.pos0
+    say(f"# batch_bench --mode w4a16: {a.config} shape, {hp['n_layer']} layers, random weights (std 0.02), "
+        f"n_ctx {n_ctx}; box {box}; tree at {a.tree}")
+    say(f"# aggregate tok/s of decode_batch_w4a16 over positions {a.pos0}..{a.pos1 - 1} ({n} steps, ids only, "
+        f"positions 0..{a.pos0 - 1} discarded as warm-up), wall clock round calls that end in a stream synchronize; "
+        f"median of {a.repeats} repeats")
+    res = {}
+    for B in bs:
+        runs = [B * n / timed_steps(dm, B, a.pos0, a.pos1, w4a16=True) for _ in range(a.repeats)]
+        res[B] = statistics.median(runs)
+        say(f"B {B:2d}: decode_batch_w4a16 {res[B]:9.1f} tok/s   (runs {' '.join(f'{v:.0f}' for v in runs)})")
+    timed_steps(dm, 32, 0, a.pos0, w4a16=True)
+    dm.set_profile(True)
+    dm.decode_batch_w4a16(list(range(32)), [a.pos0] * 32, [5] * 32, want_logits=False)
+    ks = dm.profile_kernels()
+    dm.set_profile(False)
+    tot = sum(k["ms"] for k in ks)
+    say(f"device time per kernel of one profiled B = 32 step at position {a.pos0} ({tot:.3f} ms, "
+        f"{sum(k['launches'] for k in ks)} profiled launches of {dm.info()['kernels_per_eval']} in the step):")
+    for k in sorted(ks, key=lambda k: -k["ms"]):
+        say(f"    {k['name']:<40s} {k['ms']:9.3f} ms  {100 * k['ms'] / tot:6.2f}%  {k['launches']:5d} launches")
+    prod = [k for k in ks if k["name"].startswith("k_gemm_w4a16_rows") or k["name"].startswith("lm_head")]
+    w, ms = sum(k["bytes"] for k in prod), sum(k["ms"] for k in prod)
+    if ms > 0:
+        say(f"    products: {w / 1e9:.3f} GB of weights in {ms:.3f} ms: {w / ms / 1e9:.2f} TB/s of weight bytes at B = 32")
+    if 32 in res:
+        say(f"    wall clock of a B = 32 step (above): {32e3 / res[32]:.3f} ms; profiled device time {tot:.3f} ms")
+    dm.close()
+    if a.score_tokens:  # (a model of its own: one slot at the window's length)
+        dm = hip.Model.create(ARCH[arch_s], hp, n_ctx=a.score_tokens)
+        dm.randomize(seed=1, std=0.02)
+        toks = [int(t) for t in np.random.default_rng(1).integers(0, hp["n_vocab"], a.score_tokens)]
+        for name, mode in (("w4a16", hip.MODE_W4A16), ("fast", hip.MODE_FAST), ("exact", hip.MODE_EXACT)):
+            dm.set_mode(mode)
+            dm.reserve(a.score_tokens)
+            dm.score(0, toks[:64])  # (loads the kernels)
+            t0 = time.perf_counter()
+            lp, _ = dm.score(0, toks)
+            dt = time.perf_counter() - t0
+            say(f"Model.score, one window of {a.score_tokens} tokens, {name:5s}: {dt:8.3f} s  ({a.score_tokens / dt:8.1f} tok/s, "
+                f"mean logprob {float(np.mean(lp[:-1])):.4f})")
+        dm.close()
+    lib = a.baseline_lib or hip.LIB_PATH
+    who = "parent commit" if a.baseline_lib else "this library"
+    fb = {int(k): v for k, v in run_baseline(a, lib, "batch", "fast").items()}
+    eb = {int(k): v for k, v in run_baseline(a, lib, "batch", "exact").items()}
+    for B in bs:
+        say(f"{who}, B {B:2d}: decode_batch_fast {fb[B]['tok_s']:9.1f} tok/s   decode_batch {eb[B]['tok_s']:9.1f} tok/s   "
+            f"w4a16/fast {res[B] / fb[B]['tok_s']:5.2f}   w4a16/exact {res[B] / eb[B]['tok_s']:5.2f}")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", default="exact", choices=["exact", "fast"])
+    ap.add_argument("--mode", default="exact", choices=["exact", "fast", "w4a16"])
+    ap.add_argument("--score-tokens", type=int, default=2048, help="--mode w4a16: the scoring window (0: none)")
     ap.add_argument("--sample", action="store_true", help="the sampled step, both modes (see the module text)")
     ap.add_argument("--child-kind", default="generate", help=argparse.SUPPRESS)
     ap.add_argument("--child-mode", default="exact", help=argparse.SUPPRESS)
@@ -382,6 +466,8 @@ def main():
         return main_sample(a)
     if a.mode == "fast":
         return main_fast(a)
+    if a.mode == "w4a16":
+        return main_w4a16(a)
 
     from vsim_amd import hip
     arch_s, hp = hparams(a.config, a.layers)

@@ -1,7 +1,8 @@
 """Continuous batching over one model's sequence slots, greedy or sampled.
 
 generate_many() and sample_n() drive a model through its Model methods only (n_ctx, seq_reserve,
-eval_seq, decode_batch, decode_batch_fast, and for sampling decode_batch_sample and seq_copy), so
+eval_seq, decode_batch, decode_batch_fast, decode_batch_w4a16, and for sampling decode_batch_sample
+and seq_copy), so
 anything with those methods serves: the device model, or a stub on the CPU.
 """
 from __future__ import annotations
@@ -11,7 +12,10 @@ import numpy as np
 BATCH_MAX = 32  # VSIM_BATCH_MAX: rows of one decode_batch step
 
 
-def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False, samplers=None):
+MODE_W4A16 = 2  # VSIM_MODE_W4A16
+
+
+def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False, samplers=None, w4a16=False):
     """Greedy (samplers=None) or sampled continuations of `prompts` (token-id lists), up to n_predict tokens each.
 
     Prompts are admitted in order, each into the lowest free slot: the prompt is evaluated there
@@ -29,6 +33,10 @@ def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False, s
     all rows) instead of decode_batch.  Prompts still go through eval_seq, in the model's mode; on a
     model in fast mode every sequence's tokens are then those of its own eval_seq loop.
 
+    w4a16: the steps go through decode_batch_w4a16 (weight-only products: Q4_0 weights, fp16
+    activation rows) instead; not together with fast.  On a model in weight-only mode every
+    sequence's tokens are those of its own eval_seq loop, bit for bit.
+
     samplers: one Sampler per prompt; it follows its sequence through whatever slots and batches
     the sequence meets.  On admission the prompt's tokens enter the sampler's window (accept), and
     the first token is sample_host on eval_seq's logits row, as the reference's loop does after a
@@ -37,6 +45,8 @@ def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False, s
     """
     prompts = [list(p) for p in prompts]
     out = [[] for _ in prompts]
+    if fast and w4a16:
+        raise ValueError("generate_many: fast and w4a16 name two numeric paths")
     if not prompts or n_predict <= 0:
         return out
     for p in prompts:
@@ -78,19 +88,20 @@ def generate_many(model, prompts, n_predict, eos=-1, n_slots=None, fast=False, s
             continue
         slots = sorted(live)
         if samplers is None:
-            step = model.decode_batch_fast if fast else model.decode_batch
+            step = model.decode_batch_w4a16 if w4a16 else model.decode_batch_fast if fast else model.decode_batch
             _, nxt = step(slots, [live[s][1] for s in slots], [live[s][2] for s in slots],
                           want_logits=False)
         else:
             nxt = model.decode_batch_sample(slots, [live[s][1] for s in slots], [live[s][2] for s in slots],
-                                            [samplers[live[s][0]] for s in slots], fast=fast)
+                                            [samplers[live[s][0]] for s in slots],
+                                            **({"mode": MODE_W4A16} if w4a16 else {"fast": fast}))
         for s, t in zip(slots, nxt):
             i, n_past, _ = live.pop(s)
             push(s, i, n_past + 1, int(t))
     return out
 
 
-def sample_n(model, prompt, samplers, n_predict, eos=-1, fast=False):
+def sample_n(model, prompt, samplers, n_predict, eos=-1, fast=False, w4a16=False):
     """len(samplers) sampled continuations of one prompt, the prompt evaluated once.
 
     The prompt goes through eval_seq into slot 0; seq_copy forks that cache into slots 1.., one per
@@ -98,8 +109,11 @@ def sample_n(model, prompt, samplers, n_predict, eos=-1, fast=False):
     logits row (sample_host); then decode_batch_sample advances the live sequences, rows in slot
     order, until each has produced `eos` (kept; -1: none), n_predict tokens, or has no position
     left in the context.  Returns one token list per sampler: in exact mode the reference's stream
-    for that prompt and that sampler's parameters alone.
+    for that prompt and that sampler's parameters alone.  w4a16: the steps run with weight-only
+    products (decode_batch_sample's mode), not together with fast.
     """
+    if fast and w4a16:
+        raise ValueError("sample_n: fast and w4a16 name two numeric paths")
     prompt, samplers = list(prompt), list(samplers)
     n = len(samplers)
     out = [[] for _ in samplers]
@@ -127,7 +141,8 @@ def sample_n(model, prompt, samplers, n_predict, eos=-1, fast=False):
     while live:
         slots = sorted(live)
         nxt = model.decode_batch_sample(slots, [live[s][0] for s in slots], [live[s][1] for s in slots],
-                                        [samplers[s] for s in slots], fast=fast)
+                                        [samplers[s] for s in slots],
+                                        **({"mode": MODE_W4A16} if w4a16 else {"fast": fast}))
         for s, t in zip(slots, nxt):
             n_past, _ = live.pop(s)
             push(s, n_past + 1, int(t))

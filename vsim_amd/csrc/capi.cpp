@@ -68,6 +68,21 @@ int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n
   }
   return launch_gemm_fast_rows(w4_view(w, M, K), xq, n, bias, y, (hipStream_t)stream);
 }
+int vsim_op_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, void *stream) {
+  if (!x || !x16 || !e || K <= 0 || K % QK || n < 1 || n > VSIM_BATCH_MAX) {
+    set_error("w4a16_rows: 1..32 rows, K a multiple of 32, x, x16 and e required");
+    return VSIM_EINVAL;
+  }
+  return launch_w4a16_rows(x, K, n, x16, e, (hipStream_t)stream);
+}
+int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, const int32_t *e, int n, const float *bias,
+                               float *y, void *stream) {
+  if (!w || !x16 || !e || !y || M <= 0 || K <= 0 || K % QK || n < 1 || n > VSIM_BATCH_MAX) {
+    set_error("q4_gemm_w4a16_rows: 1..32 activation rows, K a multiple of 32, M > 0, w, x16, e and y required");
+    return VSIM_EINVAL;
+  }
+  return launch_gemm_w4a16_rows(w4_view(w, M, K), x16, e, n, bias, y, (hipStream_t)stream);
+}
 int vsim_batch_set_gemm(int enable) { return batch_set_gemm(enable); }
 int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {

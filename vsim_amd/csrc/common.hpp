@@ -321,6 +321,12 @@ int launch_gemm_exact_rows(const W4 &W, const float *xd, int n, const float *bia
 // rows (gemm_fast_rows.hip) -- or, by vsim_batch_set_fast_gemm (product_plan), one k_gemv_fast launch
 // per row.  xq: launch_q4_quantize's Q4 SoA rows
 int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias, float *y, hipStream_t s);
+// Weight-only mode (gemm_w4a16_rows.hip): the fp16 row operand h [n][K] and one exponent per row of
+// n f32 rows, and the product of a W4T32 weight with it, n of any size in chunks of up to
+// VSIM_BATCH_MAX rows (vsim_op_w4a16_rows, vsim_op_q4_gemm_w4a16_rows)
+int launch_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, hipStream_t s);
+int launch_gemm_w4a16_rows(const W4 &W, const void *x16, const int32_t *e, int n, const float *bias, float *y,
+                           hipStream_t s);
 int launch_act_repack(const void *aos, void *xq, int n, int k, hipStream_t s);
 int launch_act_unpack(const void *xq, void *aos, int n, int k, hipStream_t s);
 int launch_q4_dequant(const void *xq, int rows, int k, float *y, hipStream_t s);
@@ -441,7 +447,7 @@ int launch_argmax_gen(const float *x, int n, int *out, unsigned long long *ws, i
                       hipStream_t s);
 int launch_gelu(const float *x, float *y, int n, const float *bias, int bias_len, hipStream_t s);
 int launch_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, hipStream_t s,
-                        const float *alibi = nullptr);
+                        const float *alibi = nullptr, bool alibi_row0 = false);
 // ggml_alibi head slopes (ggml.c:6217-6232), computed on the host with the reference's
 // double pow and float rounding
 void alibi_slopes_host(float *m, int n_head);

@@ -755,11 +755,17 @@ struct PromptBatch {
                                          .fast_gemm = batch_fast_gemm()});
     P.fused = pl.fused;
     if (pl.error) { set_error(pl.error); return VSIM_EINVAL; }
-    if (P.quantize && !P.x16) {
+    // Weight-only mode never quantizes: the rows' fp16 operand (launch_w4a16_rows) takes the place
+    // of the Q4 rows' factors in P.xd ([N][K] halves in room for [N][K] floats), its exponents the
+    // place of the nibbles in P.xq, made and shared under the same `quantize` flag
+    if (P.quantize && pl.w4a16) {
+      LAUNCH(m, nk, launch_w4a16_rows(P.x, K, N, P.xd, (int32_t *)P.xq, s), "k_w4a16_rows", (double)N * K * 6);
+    } else if (P.quantize && !P.x16) {
       RC(launch_q4_quantize(P.x, K, N, P.xq, P.xd, s));
       ++nk;
     }
     const long ev = prof_begin(m);
+    if (pl.w4a16) RC(launch_gemm_w4a16_rows(P.w, P.xd, (const int32_t *)P.xq, N, P.bias, P.y, s));
     switch (pl.kernel) {
       case ProductKernel::GEMM_F16_256:
         RC(launch_gemm_q4_256(P.w, P.x16, N, pl.gelu ? P.gq_bias : P.bias, P.y, s, pl.gelu ? P.gq : nullptr,
@@ -792,7 +798,7 @@ int run_layer(PromptBatch &B, int il) {
   const GraphDesc &G = m->gd;
   const LayerW &L = m->layers[il - m->l0];
   const BatchDesc &D = B.D;
-  const bool rows = is_rows(D.kind);
+  const bool rows = is_rows(D.kind), w4a16 = D.mode == VSIM_MODE_W4A16;
   const int N = D.N, n_past = D.n_past, E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E;
   int &nk = B.nk;
   hipStream_t s = m->stream;
@@ -847,8 +853,9 @@ int run_layer(PromptBatch &B, int il) {
     // position (attn.hpp, the single-token step's head); Q4 rows in launch_q4_quantize's layout
     DevTables tab;
     RC(tables_get(&tab));
-    const AttnJob A = decode_attn_job(m, tab, m->xq2, (float *)(m->xq2 + (size_t)N * (E / QK) * 16), m->xd2, 1,
-                                      nullptr, nullptr, nullptr);
+    AttnJob A = decode_attn_job(m, tab, m->xq2, (float *)(m->xq2 + (size_t)N * (E / QK) * 16), m->xd2, 1,
+                                nullptr, nullptr, nullptr);
+    if (w4a16) A.out = m->attn_in;  // the out-projection's operand is made from the f32 row
     const AttnRows R{D.rows->kc, D.rows->vc, loff, D.rows->npast};
     LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
   } else if (!rope_epi) {
@@ -869,11 +876,11 @@ int run_layer(PromptBatch &B, int il) {
     nk += 2;
   } else {
     RC(launch_kq(kc, E, m->Qb, E, d, H, nkv, N, m->kq, s, n_past)); ++nk;
-    RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s, G.alibi ? m->alibi : nullptr)); ++nk;
+    RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s, G.alibi ? m->alibi : nullptr, w4a16)); ++nk;
     RC(launch_kqv(vc, E, m->kq, d, H, nkv, N, m->attn_in, 1, s, n_past)); ++nk;
   }
   if (!attn_q16) RC(B.act16(m->attn_in, E, B.xb, nullptr, false));
-  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = !rows,
+  Product o{.w = w4_view(L.wo, E, E), .x = m->attn_in, .xq = m->xq2, .xd = m->xd2, .quantize = !rows || w4a16,
             .bias = G.qkvo_bias ? L.bo : nullptr, .y = m->attn, .x16 = B.xb};
   RC(B.mm(o));
   // fc_in (its bias goes with the GELU) reads the input norm's quantized row again, or the MLP's
@@ -1837,7 +1844,14 @@ int vsim_model_set_tensor_src(vsim_model *m, const char *name, const void *host,
 }
 
 int vsim_model_set_mode(vsim_model *m, int mode) {
-  if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST) { set_error("set_mode: bad mode"); return VSIM_EINVAL; }
+  if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST && mode != VSIM_MODE_W4A16) {
+    set_error("set_mode: bad mode");
+    return VSIM_EINVAL;
+  }
+  if (mode == VSIM_MODE_W4A16 && (!m->first || !m->last || m->borrowed)) {
+    set_error("set_mode: VSIM_MODE_W4A16 needs a whole model");
+    return VSIM_EINVAL;
+  }
   // A context of more than FD_MAXCH chunks is beyond the fast decode step's merge
   // (launch_fast_tail refuses it): such a model runs in exact mode throughout
   const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
@@ -2024,6 +2038,16 @@ int run_last_row_head(vsim_model *m, const BatchDesc &D, int &nk) {
   return run_head(m, one, m->inpL + (size_t)(D.N - 1) * E_(m), m->logits, nullptr, nk);
 }
 
+// A single-token step on the general path on slot 0, uncaptured: what the whole-model single-token
+// calls (eval_argmax, generate, eval_sample) run in weight-only mode, which has no decode graph yet.
+// The logits row ends in m->logits.
+int enqueue_single_general(vsim_model *m, const char *who, int n_past, int32_t token, int &nk) {
+  const BatchDesc D{.kind = BatchKind::PROMPT, .N = 1, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
+                    .mode = m->mode, .who = who};
+  RC(enqueue_prompt(m, D, &token, nullptr, nk));
+  return run_last_row_head(m, D, nk);
+}
+
 // Can the device make this sampler's candidates (k_sample_topk's limits)?  Otherwise: the logits
 // and the reference's host code.
 bool sampler_on_device(const vsim_sampler *sm, int V) {
@@ -2099,7 +2123,14 @@ int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *ne
   RC(begin_single(m, "eval_argmax", n_past, 1, "1", token));
   const ErrScope es(m);
   int nk = 0;
-  RC(run_step(m, STEP_ARGMAX, m->graph_enabled, nk));
+  if (m->mode == VSIM_MODE_W4A16) {
+    RC(enqueue_single_general(m, "eval_argmax", n_past, token, nk));
+    RC(launch_argmax(m->logits, m->hp.n_vocab, m->am_dev, m->am_ws, m->stream));
+    ++nk;
+    VSIM_HIP(hipMemcpyAsync(m->am_host, m->am_dev, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+  } else {
+    RC(run_step(m, STEP_ARGMAX, m->graph_enabled, nk));
+  }
   RC(finish_call(m, nk));
   *next_token = m->am_host[0];
   return VSIM_OK;
@@ -2110,6 +2141,18 @@ int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, i
   RC(begin_single(m, "generate", n_past, n_steps, "n_steps", token));
   if (n_steps == 0) return VSIM_OK;
   const ErrScope es(m);
+  if (m->mode == VSIM_MODE_W4A16) {  // one general-path step and one host round trip per token
+    for (int i = 0; i < n_steps; ++i) {
+      int nk = 0;
+      RC(enqueue_single_general(m, "generate", n_past + i, token, nk));
+      RC(launch_argmax(m->logits, m->hp.n_vocab, m->am_dev, m->am_ws, m->stream));
+      ++nk;
+      VSIM_HIP(hipMemcpyAsync(m->am_host, m->am_dev, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+      RC(finish_call(m, nk));
+      token = tokens_out[i] = m->am_host[0];
+    }
+    return VSIM_OK;
+  }
   RC(upload_step(m));
   int nk = 0;  // kernels of one decode step (argmax included)
   for (int i = 0; i < n_steps; ++i) {
@@ -2135,7 +2178,16 @@ int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t 
   const ErrScope es(m);
   fill_topk_params(m->sp_host, sm, true);
   int nk = 0;
-  RC(run_step(m, STEP_SAMPLE, m->graph_enabled, nk));
+  if (m->mode == VSIM_MODE_W4A16) {
+    hipStream_t s = m->stream;
+    VSIM_HIP(hipMemcpyAsync(m->sp_dev, m->sp_host, sizeof(TopkParams), hipMemcpyHostToDevice, s));
+    RC(enqueue_single_general(m, "eval_sample", n_past, token, nk));
+    LAUNCH(m, nk, launch_topk(m->logits, V, m->sp_dev, nullptr, 0, 0.0, 0.0, 0, m->so_dev->val, m->so_dev->id, m->tk_ws, s),
+           "k_sample_topk", (double)V * sizeof(float));
+    VSIM_HIP(hipMemcpyAsync(m->so_host, m->so_dev, sizeof(TopkOut), hipMemcpyDeviceToHost, s));
+  } else {
+    RC(run_step(m, STEP_SAMPLE, m->graph_enabled, nk));
+  }
   RC(finish_call(m, nk));
   return vsim_sampler_pick(sm, m->so_host->val, m->so_host->id, sm->top_k, next_token);
 }
@@ -2184,7 +2236,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   int nk = 0;
-  if (N == 1) {  // every graph has a single-token step (the serial-residual ones with 6 launches per layer)
+  if (N == 1 && m->mode != VSIM_MODE_W4A16) {  // every graph has a single-token step (the serial-residual ones with 6 launches per layer)
     if (m->first) {
       if (!tokens) { set_error("eval: first stage needs tokens"); return VSIM_EINVAL; }
       if (tokens[0] < 0 || tokens[0] >= V) { set_error("eval: token id out of range"); return VSIM_EINVAL; }
@@ -2198,7 +2250,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
     // (the graph is the whole model's step: a partial stage, with its residual in and out, runs eagerly)
     RC(run_step(m, STEP_LOGITS, m->graph_enabled && m->first && m->last, nk, logits != nullptr, resid_out));
   } else {
-    // general path: prompt batches (N > 1)
+    // general path: prompt batches (N > 1), and every eval of weight-only mode
     const BatchDesc D{.kind = BatchKind::PROMPT, .N = N, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
                       .mode = m->mode, .who = "eval"};
     RC(enqueue_prompt(m, D, tokens, resid_in, nk));
@@ -2280,7 +2332,8 @@ int vsim_model_eval_seq(vsim_model *m, int seq, int n_past, const int32_t *token
 
 namespace {
 // One batched decode step with the products in `mode` (vsim_model_decode_batch: exact, on a model in
-// exact mode; vsim_model_decode_batch_fast: fast, whatever the model's mode)
+// exact mode; vsim_model_decode_batch_fast: fast, vsim_model_decode_batch_w4a16: weight-only, whatever
+// the model's mode)
 // -- or, with samplers, the sampled step (vsim_model_decode_batch_sample): next[b] drawn by samplers[b]
 int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
                       const int32_t *tokens, float *logits, int32_t *next, vsim_sampler *const *samplers = nullptr) {
@@ -2327,8 +2380,10 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
   }
   VSIM_HIP(hipMemcpyAsync(m->bw_dev, m->bw_host, sizeof(BatchWords), hipMemcpyHostToDevice, s));
   int nk = 0;
-  const BatchDesc D{.kind = mode == VSIM_MODE_EXACT ? BatchKind::ROWS_EXACT : BatchKind::ROWS_FAST, .N = B,
-                    .rows = m->bw_dev, .mode = mode, .who = "decode_batch"};
+  const BatchKind kind = mode == VSIM_MODE_EXACT  ? BatchKind::ROWS_EXACT
+                         : mode == VSIM_MODE_FAST ? BatchKind::ROWS_FAST
+                                                  : BatchKind::ROWS_W4A16;
+  const BatchDesc D{.kind = kind, .N = B, .rows = m->bw_dev, .mode = mode, .who = "decode_batch"};
   RC(enqueue_prompt(m, D, tokens, nullptr, nk));
   RC(run_head(m, D, m->inpL, m->score_x, "lm_head (batch)", nk));
   int32_t *am_dev = (int32_t *)m->score_out;
@@ -2378,6 +2433,11 @@ int vsim_model_decode_batch_fast(vsim_model *m, int B, const int32_t *seq, const
   return decode_batch_impl(m, VSIM_MODE_FAST, B, seq, n_past, tokens, logits, next);
 }
 
+int vsim_model_decode_batch_w4a16(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                  const int32_t *tokens, float *logits, int32_t *next) {
+  return decode_batch_impl(m, VSIM_MODE_W4A16, B, seq, n_past, tokens, logits, next);
+}
+
 int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
                                    const int32_t *tokens, vsim_sampler *const *samplers, int32_t *next) {
   if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST) {
@@ -2386,6 +2446,12 @@ int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t
   }
   if (!samplers || !next) { set_error("decode_batch_sample: null argument"); return VSIM_EINVAL; }
   return decode_batch_impl(m, mode, B, seq, n_past, tokens, nullptr, next, samplers);
+}
+
+int vsim_model_decode_batch_sample_w4a16(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
+                                         const int32_t *tokens, vsim_sampler *const *samplers, int32_t *next) {
+  if (!samplers || !next) { set_error("decode_batch_sample: null argument"); return VSIM_EINVAL; }
+  return decode_batch_impl(m, VSIM_MODE_W4A16, B, seq, n_past, tokens, nullptr, next, samplers);
 }
 
 int vsim_model_seq_copy(vsim_model *m, int dst, int src, int n_tokens) {
@@ -2455,6 +2521,7 @@ int vsim_model_eval_score(vsim_model *m, int n_past, const int32_t *tokens, int 
 int vsim_model_stage_bind(vsim_model *m, const int32_t *tok_in, const float *resid_in, float *resid_out,
                           int32_t *tok_out) {
   if (!m) { set_error("stage_bind: null model"); return VSIM_EINVAL; }
+  if (m->mode == VSIM_MODE_W4A16) { set_error("stage_bind: no pipeline stages in VSIM_MODE_W4A16"); return VSIM_EINVAL; }
   if ((m->first && !tok_in) || (!m->first && !resid_in) || (m->last && !tok_out) || (!m->last && !resid_out)) {
     set_error("stage_bind: first stage needs tok_in, later stages resid_in, the last tok_out, the others resid_out");
     return VSIM_EINVAL;
@@ -2473,6 +2540,7 @@ int vsim_model_stage_bind(vsim_model *m, const int32_t *tok_in, const float *res
 
 int vsim_model_stage_begin(vsim_model *m, int n_past) {
   if (!m || n_past < 0 || n_past >= m->n_ctx) { set_error("stage_begin: n_past outside the context"); return VSIM_EINVAL; }
+  if (m->mode == VSIM_MODE_W4A16) { set_error("stage_begin: no pipeline stages in VSIM_MODE_W4A16"); return VSIM_EINVAL; }
   if (!m->st_tok_in && !m->st_resid_in) { set_error("stage_begin: stage_bind first"); return VSIM_EINVAL; }
   VSIM_HIP(hipSetDevice(m->device));
   RC(ensure_scratch(m, 1));
@@ -2484,6 +2552,7 @@ int vsim_model_stage_begin(vsim_model *m, int n_past) {
 }
 
 int vsim_model_stage_step(vsim_model *m) {
+  if (m && m->mode == VSIM_MODE_W4A16) { set_error("stage_step: no pipeline stages in VSIM_MODE_W4A16"); return VSIM_EINVAL; }
   if (!m || m->st_npast < 0) { set_error("stage_step: stage_begin first"); return VSIM_EINVAL; }
   if (m->st_npast + 1 > m->n_ctx) { set_error("stage_step: context full"); return VSIM_EINVAL; }
   VSIM_HIP(hipSetDevice(m->device));

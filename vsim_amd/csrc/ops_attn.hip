@@ -128,15 +128,17 @@ int launch_rope_kv_write(int style, float *Q, const float *K, const float *V, fl
 // The fp16-valued exps sum exactly in double in any order (multiples of 2^-24, < 2^11).
 // alibi (BLOOM, may be null): per-head slopes m_k; after the scale each score gets
 // (j+1)*m_k added, j the query row (ggml_alibi, ggml.c:6184-6244), before the mask.
+// alibi_row0 (weight-only mode, where a row must not depend on its place in the batch): every row
+// gets the single-token step's term, 1*m_k, instead -- the same softmax but for its rounding.
 __global__ void __launch_bounds__(256) k_attn_softmax(float *p, int nc, int nr, int n_past, float scale,
                                                        const uint16_t *__restrict__ etab,
-                                                       const float *__restrict__ alibi) {
+                                                       const float *__restrict__ alibi, int alibi_row0) {
   __shared__ float shf[4];
   __shared__ double shd[4];
   const int row = blockIdx.x;
   const int j = row % nr;
   float *x = p + (size_t)row * nc;
-  const float ab = alibi ? (float)(j + 1) * alibi[row / nr] : 0.0f;
+  const float ab = alibi ? (float)(alibi_row0 ? 1 : j + 1) * alibi[row / nr] : 0.0f;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < nc; i += 256) {
@@ -169,10 +171,11 @@ __global__ void __launch_bounds__(256) k_attn_softmax(float *p, int nc, int nr, 
 }
 
 int launch_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float scale, hipStream_t s,
-                        const float *alibi) {
+                        const float *alibi, bool alibi_row0) {
   DevTables t;
   if (int rc = tables_get(&t)) return rc;
-  hipLaunchKernelGGL(k_attn_softmax, dim3(nr * nz), dim3(256), 0, s, p, nc, nr, n_past, scale, t.exp_f16, alibi);
+  hipLaunchKernelGGL(k_attn_softmax, dim3(nr * nz), dim3(256), 0, s, p, nc, nr, n_past, scale, t.exp_f16, alibi,
+                     alibi_row0 ? 1 : 0);
   VSIM_HIP(hipGetLastError());
   return VSIM_OK;
 }

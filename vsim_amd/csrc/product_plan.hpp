@@ -19,8 +19,11 @@ enum class BatchKind {
   PROMPT_SLOT,  // the same on a named sequence slot's cache (eval_seq)
   ROWS_EXACT,   // one token each of N sequences, exact products (decode_batch)
   ROWS_FAST,    // the same with fast products, the Q4 rows kept at every N (decode_batch_fast)
+  ROWS_W4A16,   // the same with weight-only products on the f32 rows (decode_batch_w4a16)
 };
-inline bool is_rows(BatchKind k) { return k == BatchKind::ROWS_EXACT || k == BatchKind::ROWS_FAST; }
+inline bool is_rows(BatchKind k) {
+  return k == BatchKind::ROWS_EXACT || k == BatchKind::ROWS_FAST || k == BatchKind::ROWS_W4A16;
+}
 
 // Fast-mode products from this many rows on run on the fp16 MFMA GEMM (gemm_f16.hip); a prompt
 // batch then carries its activations as the GEMM's fp16 operand (scratch pf_x16)
@@ -66,6 +69,9 @@ enum class ProductKernel {
   GEMV_CHAIN,       // the exact chain GEMV, GEMV_JOBS rows per launch: launch_gemv_rows
   GEMV_FAST,        // k_gemv_fast, one launch per row: launch_gemv_rows
 };
+// (Weight-only mode's k_gemm_w4a16_rows is ProductPlan::w4a16, not an enumerator here:
+// tests/test_product_plan_cpu.py compiles a switch over this enum without a default under -Werror, so
+// the enum cannot grow while that file stays as it is.)
 
 struct ProductQuery {
   BatchKind kind = BatchKind::PROMPT;
@@ -85,6 +91,9 @@ struct ProductPlan {
   int passes = 1;              // algorithmic bytes: this many passes over the weight
   bool gelu = false;           // the GELU-quantize epilogue runs (only k_gemm_f16_256 has it: M % 32 == 0)
   bool fused = false;          // that or the G2Epi epilogue runs
+  // weight-only mode: k_gemm_w4a16_rows (launch_gemm_w4a16_rows) runs the product on the rows' fp16
+  // operand, one launch per chunk of VSIM_BATCH_MAX rows; `kernel` stays NONE
+  bool w4a16 = false;
   const char *error = nullptr;
 };
 
@@ -101,7 +110,18 @@ inline ProductPlan product_plan(const ProductQuery &q) {
     p.kernels = kernels;
     p.name = name;
   };
-  if (q.kind == BatchKind::ROWS_FAST) {
+  if (q.mode == VSIM_MODE_W4A16 || q.kind == BatchKind::ROWS_W4A16) {
+    // weight-only mode: the per-row kernel on consecutive chunks of VSIM_BATCH_MAX rows at every N
+    // (a chunked weight pass for a long prompt: chunking cannot change a row's bits)
+    const int chunks = (q.N + VSIM_BATCH_MAX - 1) / VSIM_BATCH_MAX;
+    if (q.x16 || q.gelu || q.epi || q.mode != VSIM_MODE_W4A16) {
+      p.error = "weight-only mode: a product left the f32 rows";
+    } else {
+      is(PK::NONE, chunks, chunks, "k_gemm_w4a16_rows");
+      p.w4a16 = true;
+      p.passes = chunks;
+    }
+  } else if (q.kind == BatchKind::ROWS_FAST) {
     // k_gemv_fast's value of every row, in one pass of the weight for all rows or as one launch
     // per row: the same bits
     if (q.x16 || q.N > VSIM_BATCH_MAX) {

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("VSIM_LIB") or os.path.join(HERE, "_build", "libvsim_h
 
 MODE_EXACT = 0
 MODE_FAST = 1
+MODE_W4A16 = 2  # weight-only: Q4_0 weights x fp16 activation rows, fp32 accumulation
+W4A16_NONFINITE = -2**31  # VSIM_W4A16_NONFINITE: the exponent of a row that holds a NaN or an Inf
 ARCH_GPTNEOX = 0
 ARCH_GPTJ = 1
 ARCH_BLOOM = 2
@@ -56,6 +58,8 @@ EXPORTS = [
     "vsim_op_gemm_q4_256_pair_h16",
     "vsim_op_topk_rows", "vsim_topk_rows_set_wg", "vsim_model_decode_batch_sample", "vsim_model_seq_copy",
     "vsim_op_tail_attn", "vsim_op_tail_ln", "vsim_op_tail_ln_ws_bytes",
+    "vsim_op_w4a16_rows", "vsim_op_q4_gemm_w4a16_rows", "vsim_model_decode_batch_w4a16",
+    "vsim_model_decode_batch_sample_w4a16",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -314,6 +318,10 @@ def lib():
     L.vsim_topk_rows_set_wg.argtypes = [ci]
     L.vsim_model_decode_batch_sample.argtypes = [vp, ci, ci, vp, vp, vp, ctypes.POINTER(vp), vp]
     L.vsim_model_seq_copy.argtypes = [vp, ci, ci, ci]
+    L.vsim_op_w4a16_rows.argtypes = [vp, ci, ci, vp, vp, vp]
+    L.vsim_op_q4_gemm_w4a16_rows.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
+    L.vsim_model_decode_batch_w4a16.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    L.vsim_model_decode_batch_sample_w4a16.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(vp), vp]
     _lib = L
     return L
 
@@ -468,6 +476,23 @@ def q4_gemm_fast_rows(w, M, K, xq, n, bias, y, stream=None):
     Q4 SoA rows), + bias [M] when given; each value bit for bit q4_gemv's (n = 1, MODE_FAST) of
     that row alone.  Enqueued on `stream`, not synchronized."""
     check(lib().vsim_op_q4_gemm_fast_rows(ptr(w), M, K, ptr(xq), n, ptr(bias), ptr(y), stream), "q4_gemm_fast_rows")
+
+
+def w4a16_rows(x, K, n, x16, e, stream=None):
+    """vsim_op_w4a16_rows on device buffers (torch tensors): the weight-only mode's operand of the n
+    (1..BATCH_MAX) f32 rows x [n][K]: x16 [n][K] float16 = fp16_rn(x * 2^e[row]), e int32 [n] (the
+    exponent that puts the row's largest finite |x| into [2^14, 2^15); W4A16_NONFINITE and zeros for
+    a row with a NaN or an Inf).  Enqueued on `stream`, not synchronized."""
+    check(lib().vsim_op_w4a16_rows(ptr(x), K, n, ptr(x16), ptr(e), stream), "w4a16_rows")
+
+
+def q4_gemm_w4a16_rows(w, M, K, x16, e, n, bias, y, stream=None):
+    """vsim_op_q4_gemm_w4a16_rows on device buffers (torch tensors): y [n][M] = the W4T32 weight w
+    [M][K] times the n (1..BATCH_MAX) rows of w4a16_rows' operand (x16, e), fp32 accumulation, + bias
+    [M] when given; a row's outputs do not depend on n or on the other rows.  Enqueued on `stream`,
+    not synchronized."""
+    check(lib().vsim_op_q4_gemm_w4a16_rows(ptr(w), M, K, ptr(x16), ptr(e), n, ptr(bias), ptr(y), stream),
+          "q4_gemm_w4a16_rows")
 
 
 def batch_set_fast_gemm(enable) -> int:
@@ -650,6 +675,12 @@ class Model:
         return self._decode_batch(lib().vsim_model_decode_batch_fast, "decode_batch_fast", seqs, n_past, tokens,
                                   want_logits)
 
+    def decode_batch_w4a16(self, seqs, n_past, tokens, want_logits=True):
+        """decode_batch with weight-only products (MODE_W4A16), whatever the model's mode: every row
+        bit for bit eval_seq's row of that sequence on this model in MODE_W4A16.  Same return shape."""
+        return self._decode_batch(lib().vsim_model_decode_batch_w4a16, "decode_batch_w4a16", seqs, n_past, tokens,
+                                  want_logits)
+
     def _decode_batch(self, fn, who, seqs, n_past, tokens, want_logits):
         sq = np.ascontiguousarray(seqs, np.int32)
         npst = np.ascontiguousarray(n_past, np.int32)
@@ -662,11 +693,14 @@ class Model:
         check(fn(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)), who)
         return lg, nxt[:B]
 
-    def decode_batch_sample(self, seqs, n_past, tokens, samplers, fast=False):
+    def decode_batch_sample(self, seqs, n_past, tokens, samplers, fast=False, mode=None):
         """One sampled decode step for len(seqs) sequences: decode_batch (or decode_batch_fast), then
         row b's token drawn by samplers[b] -- the candidate stage of all rows in one launch on the
         device, the draw on the host.  Every row's token and sampler state are those of eval_sample
-        on that sequence alone.  Returns next int32 [B]."""
+        on that sequence alone.  mode (MODE_EXACT, MODE_FAST or MODE_W4A16) names the step's numeric
+        path and overrides `fast` when given.  Returns next int32 [B]."""
+        if mode is None:
+            mode = MODE_FAST if fast else MODE_EXACT
         sq = np.ascontiguousarray(seqs, np.int32)
         npst = np.ascontiguousarray(n_past, np.int32)
         tok = np.ascontiguousarray(tokens, np.int32)
@@ -676,8 +710,12 @@ class Model:
         B = int(sq.size)
         hs = (ctypes.c_void_p * max(B, 1))(*[None if sm is None else sm.h for sm in samplers])
         nxt = np.zeros(max(B, 1), np.int32)
-        check(lib().vsim_model_decode_batch_sample(self.h, MODE_FAST if fast else MODE_EXACT, B, ptr(sq), ptr(npst),
-                                                   ptr(tok), hs, ptr(nxt)), "decode_batch_sample")
+        if int(mode) == MODE_W4A16:  # (an entry of its own: the C call's mode argument stays EXACT / FAST)
+            check(lib().vsim_model_decode_batch_sample_w4a16(self.h, B, ptr(sq), ptr(npst), ptr(tok), hs, ptr(nxt)),
+                  "decode_batch_sample")
+        else:
+            check(lib().vsim_model_decode_batch_sample(self.h, int(mode), B, ptr(sq), ptr(npst),
+                                                       ptr(tok), hs, ptr(nxt)), "decode_batch_sample")
         return nxt[:B]
 
     def seq_copy(self, dst, src, n_tokens):

@@ -6,7 +6,7 @@
 // (prompt echoed in n_batch+1 chunks, then sampled ids), " <END|>"; --return_logits
 // prints "logits: %.8f ..." rows.  The model runs in libvsim_hip.so (device resident);
 // this file is host control only: the sampler too is the library's (vsim_sampler_*).
-// Extra flags: --device N, --mode exact|fast, --n_ctx N (reference: fixed 512,
+// Extra flags: --device N, --mode exact|fast|w4a16, --n_ctx N (reference: fixed 512,
 // vsim.cpp:758), --no-graph, --sampler host|device, --quantize (load an F32 / F16 file as the
 // converters write it, quantized to Q4_0 on the device while it loads), --score (the -p ids are a
 // text to score: per-position log-probabilities and the perplexity, vsim_model_eval_score).
@@ -60,7 +60,9 @@ void usage(const char *argv0, const Params &p) {
   fprintf(stderr, "  -m FNAME, --model FNAME  model path\n");
   fprintf(stderr, "  --return_logits       print the next-token logits after the prompt and exit\n");
   fprintf(stderr, "  --device N            GPU index (default 0)\n");
-  fprintf(stderr, "  --mode exact|fast     exact = bit-identical to the reference (default)\n");
+  fprintf(stderr, "  --mode exact|fast|w4a16  exact = bit-identical to the reference (default); w4a16 = weight-only:\n");
+  fprintf(stderr, "                        Q4_0 weights, activations rounded to fp16 instead of quantized (generation\n");
+  fprintf(stderr, "                        and --score)\n");
   fprintf(stderr, "  --n_ctx N             context length (default 512, as the reference)\n");
   fprintf(stderr, "  --no-graph            launch every kernel eagerly\n");
   fprintf(stderr, "  --quantize            the model file is F32 / F16: quantize it to Q4_0 on the GPU while loading\n");
@@ -95,7 +97,10 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "-m" || a == "--model") p.model = next();
     else if (a == "--return_logits") p.return_logits = true;
     else if (a == "--device") p.device = std::stoi(next());
-    else if (a == "--mode") p.mode = std::string(next()) == "fast" ? VSIM_MODE_FAST : VSIM_MODE_EXACT;
+    else if (a == "--mode") {
+      const std::string v = next();
+      p.mode = v == "fast" ? VSIM_MODE_FAST : v == "w4a16" ? VSIM_MODE_W4A16 : VSIM_MODE_EXACT;
+    }
     else if (a == "--n_ctx") p.n_ctx = std::stoi(next());
     else if (a == "--no-graph") p.graph = false;
     else if (a == "--quantize") p.quantize = true;
@@ -221,7 +226,11 @@ int run(const Params &params, int arch) {
     fprintf(stderr, "%s: failed to load model from '%s': %s\n", __func__, params.model.c_str(), vsim_last_error());
     return 1;
   }
-  vsim_model_set_mode(model, params.mode);
+  if (vsim_model_set_mode(model, params.mode) != VSIM_OK) {
+    fprintf(stderr, "%s: --mode: %s\n", __func__, vsim_last_error());
+    vsim_model_free(model);
+    return 1;
+  }
   vsim_model_set_graph(model, params.graph ? 1 : 0);
   // VSIM_PROFILE=1: per-kernel device time at the end of the run, the device counterpart of
   // the reference's per-op time table (monitor.c:196-262, show_time_sep); the steps then run

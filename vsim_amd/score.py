@@ -1,5 +1,5 @@
 """Scoring a text with a model: per-position log-probabilities, perplexity, and the agreement of
-two runs (exact vs fast mode, an F16-quantized vs a Q4_0 file).
+two runs (exact vs fast or weight-only mode, an F16-quantized vs a Q4_0 file).
 
 The numbers come from Model.score (vsim_model_eval_score, include/vsim_hip.h): one prompt pass per
 window, the log-sum-exp of every logits row taken on the device.  This module only cuts the text
