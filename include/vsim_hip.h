@@ -346,6 +346,75 @@ typedef struct {
 } vsim_tail_ln_args;
 size_t vsim_op_tail_ln_ws_bytes(int E); /* 0 for an E that is no positive multiple of 32 */
 int vsim_op_tail_ln(const vsim_tail_ln_args *a, void *stream);
+/* The exact decode step's LayerNorm launch (k_ln_quant: 8 slice workgroups of 512 threads per norm)
+ * on the call's operands, one launch_ln_quant:
+ *   v[i]   = x[i]                                     no join operand
+ *          = x[i] + ((ja[i] + jab[i]) + (jf[i] + jfb[i]))   in float32; jab NULL: ja[i] alone, jfb NULL:
+ *            jf[i] alone; ja NULL: x[i] + (jf[i] + jfb[i]); jf NULL: x[i] + (ja[i] + jab[i])
+ *            (the four forms the model's graphs use) -> jout when given
+ *   y      = ggml_compute_forward_norm_f32 of v, as vsim_op_tail_ln's
+ *   z1     = w1 * y + b1 (two float roundings), quantize_row_q4_0 -> q1 (Q4 SoA: nibbles [n/32][16], then
+ *            scales [n/32]) and its factors xd1 [n], as vsim_op_q4_quantize's of z1
+ *   z2     likewise with w2, b2 into q2, xd2 when all four are given (none: one norm).  The second
+ *            norm is a job of its own in the launch: it joins the same operands and stores no jout.
+ *   *epoch += 1 when epoch is given (a device word: the decode step's tag counter).
+ * Bit for bit the reference's values.  How the kernel gets there shows only in vsim_norm_fallbacks:
+ * every slice workgroup computes the whole row's statistics, slice 0 of each norm counts, so a call
+ * adds at most one per norm to each counter ([0] the mean certificate failed and the sum was redone
+ * in order, [1] the scale interval was ambiguous and the sum of squares was redone in order).
+ * VSIM_EINVAL for what the launch cannot take: n no positive multiple of 32 or beyond the 64 KB of
+ * dynamic LDS the row needs (n <= 16320), x, w1, b1, q1 or xd1 missing, an incomplete second norm,
+ * jab without ja, jfb without jf, jout without a join operand, jout overlapping an input (the
+ * slices read the whole of every input while others store), or x, w*, b*, j* not 16-byte aligned
+ * (float4 accesses), q*, xd*, epoch not 4-byte aligned.  Enqueued on stream, not synchronized. */
+typedef struct {
+  const float *x;              /* [n] the row (the residual in) */
+  int32_t n;
+  const float *w1, *b1;        /* [n] norm 1 affine */
+  void *q1;                    /* norm 1 as Q4 SoA */
+  float *xd1;                  /* [n] its factors */
+  const float *w2, *b2;        /* norm 2: all four or none */
+  void *q2;
+  float *xd2;
+  const float *ja, *jab;       /* [n] optional join operands, see above */
+  const float *jf, *jfb;
+  float *jout;                 /* [n] the joined row, or NULL */
+  uint32_t *epoch;             /* device word advanced by one, or NULL */
+} vsim_ln_quant_args;
+int vsim_op_ln_quant(const vsim_ln_quant_args *a, void *stream);
+/* The exact decode step's GEMV batch ({fc_in + bias + GELU + requantize, Q, K, V} in the model): one
+ * launch_gemv_chain_batch in exact mode on nj = 1..4 jobs, workgroups taking job 0's rows, then job
+ * 1's, ...  Per job y = W . xd in the reference's chain (vsim_op_q4_gemv's, on the factors xd of
+ * vsim_op_q4_quantize), then
+ *   gelu_q == 0:  y[row] = dot (+ bias[row])
+ *   gelu_q != 0:  g = gelu table[fp16(dot + bias[row])] (the library's table, vsim_op_tables), y[row] =
+ *                 g when y is given, and each 32 rows quantize_row_q4_0 into block row/32 of oq (Q4 SoA,
+ *                 M/32 blocks) and oxd [M], as vsim_op_q4_quantize's of g -- also where a block mixes
+ *                 the table's NaN (for -inf) or inf with finite values: quantize_row_q4_0's amax =
+ *                 MAX(amax, fabsf(v)) in element order (a NaN replaces the maximum, the next element
+ *                 the NaN) and its unmasked vi0 | vi1 << 4 for codes outside 0..15.
+ * A job's outputs do not depend on the jobs beside it.  *kernel (host, may be NULL) reports what
+ * the launch chose for the batch: 1 k_gemv_solo (the jobs have at least 192 groups of 64 rows), 0
+ * k_gemv_chain32.
+ * VSIM_EINVAL for nj outside 1..4, M <= 0, K no positive multiple of 32, a NULL w or xd, a NULL y
+ * without gelu_q, gelu_q with a NULL bias, oq or oxd or with M % 32 != 0, w or xd not 16-byte aligned
+ * (16-byte weight loads and LDS-DMA of the factors), bias, y, oq or oxd not 4-byte aligned.  w holds
+ * vsim_q4_bytes(M, K) bytes (whole 32-row tiles).  Enqueued on stream, not synchronized. */
+typedef struct {
+  const void *w;               /* W4T32 [M][K] */
+  int32_t M, K;
+  const float *xd;             /* [K] activation factors */
+  const float *bias;           /* [M] or NULL (required with gelu_q) */
+  float *y;                    /* [M], or NULL with gelu_q */
+  int32_t gelu_q;
+  void *oq;                    /* gelu_q: the output row as Q4 SoA (nibbles [M/32][16], then scales [M/32]) */
+  float *oxd;                  /* gelu_q: [M] its factors */
+} vsim_gemv_batch_job;
+typedef struct {
+  vsim_gemv_batch_job j[4];
+  int32_t nj;
+} vsim_gemv_batch_args;
+int vsim_op_gemv_batch(const vsim_gemv_batch_args *a, int32_t *kernel, void *stream);
 /* Long-prompt GEMM pieces (fast mode, N >= 256 inside the model): the fp16 image [M][K] of a
  * W4T32 weight (values d*(q-8) rounded to fp16), and Y[n][m] (+bias[m]) = sum_k W16[m][k] *
  * X16[n][k] on the 256 x 256-tile fp16 MFMA GEMM (K % 64 == 0; X16 [n][K] fp16). */

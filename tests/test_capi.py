@@ -136,10 +136,14 @@ def test_fp16_tables_match_reference():
 
 
 def test_ctypes_tail_ln_args_layout():
-    """vsim_amd.hip.TailLnArgs and AttnBatchArgs have the layout a C compiler gives
-    vsim_tail_ln_args and vsim_attn_batch_args (include/vsim_hip.h)."""
+    """vsim_amd.hip.TailLnArgs, AttnBatchArgs, LnQuantArgs, GemvBatchJob and GemvBatchArgs have the
+    layout a C compiler gives vsim_tail_ln_args, vsim_attn_batch_args, vsim_ln_quant_args,
+    vsim_gemv_batch_job and vsim_gemv_batch_args (include/vsim_hip.h)."""
     import ctypes
-    structs = {"vsim_tail_ln_args": hip.TailLnArgs, "vsim_attn_batch_args": hip.AttnBatchArgs}
+    structs = {"vsim_tail_ln_args": hip.TailLnArgs, "vsim_attn_batch_args": hip.AttnBatchArgs,
+               "vsim_ln_quant_args": hip.LnQuantArgs, "vsim_gemv_batch_job": hip.GemvBatchJob,
+               "vsim_gemv_batch_args": hip.GemvBatchArgs}
+    assert {"vsim_op_ln_quant", "vsim_op_gemv_batch"} <= exported_symbols() & set(hip.EXPORTS)
     lines = []
     for cname, cls in structs.items():
         lines += [f'printf("{cname}.{f} %zu\\n", offsetof({cname}, {f}));' for f, _ in cls._fields_]

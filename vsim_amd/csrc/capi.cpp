@@ -355,6 +355,110 @@ int vsim_op_tail_ln(const vsim_tail_ln_args *t, void *stream) {
   if (buf) (void)hipFree(buf);
   return rc;
 }
+// k_ln_quant on the call's operands: launch_ln_quant(j1, two ? &j2 : nullptr, n, s), the second
+// job joining the same operands without storing them (model.cpp's join_into(j2, false)).
+int vsim_op_ln_quant(const vsim_ln_quant_args *a, void *stream) {
+  // the row in dynamic LDS beside ln_exact_lds_t's static words, within the 64 KB a launch gets unasked
+  constexpr int LNQ_MAX_N = (65536 - 256) / 4 / QK * QK;
+  if (!a || a->n <= 0 || a->n % QK || a->n > LNQ_MAX_N) {
+    set_error("ln_quant: n must be a positive multiple of 32, at most 16320 (the row lives in 64 KB of LDS)");
+    return VSIM_EINVAL;
+  }
+  if (!a->x || !a->w1 || !a->b1 || !a->q1 || !a->xd1) {
+    set_error("ln_quant: x, w1, b1, q1 and xd1 are required");
+    return VSIM_EINVAL;
+  }
+  const bool two = a->w2 || a->b2 || a->q2 || a->xd2;
+  if (two && (!a->w2 || !a->b2 || !a->q2 || !a->xd2)) {
+    set_error("ln_quant: the second norm needs w2, b2, q2 and xd2");
+    return VSIM_EINVAL;
+  }
+  if ((a->jab && !a->ja) || (a->jfb && !a->jf)) {
+    set_error("ln_quant: a join bias without its operand (jab needs ja, jfb needs jf)");
+    return VSIM_EINVAL;
+  }
+  if (a->jout && !a->ja && !a->jf) {
+    set_error("ln_quant: jout without a join operand is never written");
+    return VSIM_EINVAL;
+  }
+  const size_t nbytes = (size_t)a->n * sizeof(float);
+  const void *ins[] = {a->x, a->w1, a->b1, a->w2, a->b2, a->ja, a->jab, a->jf, a->jfb};
+  for (const void *p : ins) {
+    if ((uintptr_t)p & 15) {
+      set_error("ln_quant: x, the affines and the join operands must be 16-byte aligned");
+      return VSIM_EINVAL;
+    }
+    if (p && a->jout && (uintptr_t)p < (uintptr_t)a->jout + nbytes && (uintptr_t)a->jout < (uintptr_t)p + nbytes) {
+      set_error("ln_quant: jout overlaps an input (every slice workgroup reads the whole row)");
+      return VSIM_EINVAL;
+    }
+  }
+  if (((uintptr_t)a->jout & 15) || (((uintptr_t)a->q1 | (uintptr_t)a->xd1 | (uintptr_t)a->q2 | (uintptr_t)a->xd2 |
+                                      (uintptr_t)a->epoch) & 3)) {
+    set_error("ln_quant: jout must be 16-byte aligned, q1, xd1, q2, xd2 and epoch 4-byte aligned");
+    return VSIM_EINVAL;
+  }
+  DevTables tab;
+  RC(tables_get(&tab));  // (the device's fallback counters come with its tables)
+  const size_t nblk = (size_t)(a->n / QK);
+  LnQuantJob j1{a->x, a->w1, a->b1, (uint8_t *)a->q1, (float *)((uint8_t *)a->q1 + nblk * 16), a->xd1};
+  j1.ja = a->ja;
+  j1.jab = a->jab;
+  j1.jf = a->jf;
+  j1.jfb = a->jfb;
+  LnQuantJob j2 = j1;  // the same row and join, no jout, no epoch
+  j1.jout = a->jout;
+  j1.ep = a->epoch;
+  if (two) {
+    j2.w = a->w2;
+    j2.b = a->b2;
+    j2.qs = (uint8_t *)a->q2;
+    j2.d = (float *)((uint8_t *)a->q2 + nblk * 16);
+    j2.xd = a->xd2;
+  }
+  return launch_ln_quant(j1, two ? &j2 : nullptr, a->n, (hipStream_t)stream);
+}
+// launch_gemv_chain_batch (k_gemv_solo or k_gemv_chain32, as gemv_chain_solo decides) on the call's jobs.
+int vsim_op_gemv_batch(const vsim_gemv_batch_args *a, int32_t *kernel, void *stream) {
+  if (!a || a->nj < 1 || a->nj > 4) { set_error("gemv_batch: 1 to 4 jobs"); return VSIM_EINVAL; }
+  GemvBatch B{};
+  B.nj = a->nj;
+  bool gelu = false;
+  for (int i = 0; i < a->nj; ++i) {
+    const vsim_gemv_batch_job &j = a->j[i];
+    if (!j.w || !j.xd || j.M <= 0 || j.K <= 0 || j.K % QK || (!j.gelu_q && !j.y) ||
+        (j.gelu_q && (!j.bias || !j.oq || !j.oxd || j.M % T32))) {
+      set_error("gemv_batch: bad job (w, xd, M > 0, K a positive multiple of 32; y unless gelu_q; gelu_q needs "
+                "bias, oq, oxd and whole 32-row tiles)");
+      return VSIM_EINVAL;
+    }
+    if ((((uintptr_t)j.w | (uintptr_t)j.xd) & 15) ||
+        (((uintptr_t)j.bias | (uintptr_t)j.y | (uintptr_t)j.oq | (uintptr_t)j.oxd) & 3)) {
+      set_error("gemv_batch: w and xd must be 16-byte aligned, bias, y, oq and oxd 4-byte aligned");
+      return VSIM_EINVAL;
+    }
+    GemvJob &J = B.j[i];
+    J.w = w4_view(j.w, j.M, j.K);
+    J.xd = j.xd;
+    J.bias = j.bias;
+    J.y = j.y;
+    J.epi = j.gelu_q ? EPI_GELU_Q : EPI_STORE;
+    if (j.gelu_q) {
+      J.oq_qs = (uint8_t *)j.oq;
+      J.oq_d = (float *)((uint8_t *)j.oq + (size_t)(j.M / QK) * 16);
+      J.oxd = j.oxd;
+      gelu = true;
+    }
+  }
+  if (gelu) {
+    DevTables tab;
+    RC(tables_get(&tab));
+    for (int i = 0; i < a->nj; ++i)
+      if (B.j[i].epi == EPI_GELU_Q) B.j[i].gelu_tab = tab.gelu_f16;
+  }
+  if (kernel) *kernel = gemv_chain_solo(B) ? 1 : 0;
+  return launch_gemv_chain_batch(B, (hipStream_t)stream);
+}
 int vsim_op_q4_expand_f16(const void *w, int M, int K, void *w16, void *stream) {
   if (!w || !w16 || M <= 0 || K <= 0 || K % QK) { set_error("q4_expand_f16: bad argument"); return VSIM_EINVAL; }
   return launch_w4_expand_f16(w4_view(w, M, K), w16, (hipStream_t)stream);

@@ -270,7 +270,8 @@ __device__ __forceinline__ void chain32_body(const GemvBatch &B, int t, C2Lds<S>
       g = h2f(B.j[ji].gelu_tab[f2h(acc + bias[row])]);
       if (y) y[row] = g;
     }
-    quantize_half(g, lane, ok, B.j[ji].oq_qs + (size_t)t * 16, B.j[ji].oq_d + t, B.j[ji].oxd + (size_t)t * QK);
+    quantize_half<false, true>(g, lane, ok, B.j[ji].oq_qs + (size_t)t * 16, B.j[ji].oq_d + t,
+                               B.j[ji].oxd + (size_t)t * QK);
   } else if (lane < 32 && row < rows) {
     y[row] = bias ? acc + bias[row] : acc;
   }
@@ -1243,8 +1244,8 @@ __device__ __forceinline__ void solo_body(const GemvBatch &B, int g, float (*P)[
       if (y) y[row] = gv;
     }
     const int blk = row / QK;
-    quantize_half(gv, lane, ok, B.j[ji].oq_qs + (size_t)blk * 16, B.j[ji].oq_d + blk,
-                  B.j[ji].oxd + (size_t)blk * QK);
+    quantize_half<false, true>(gv, lane, ok, B.j[ji].oq_qs + (size_t)blk * 16, B.j[ji].oq_d + blk,
+                               B.j[ji].oxd + (size_t)blk * QK);
   } else if (row < rows) {
     y[row] = bias ? acc + bias[row] : acc;
   }

@@ -499,38 +499,65 @@ __device__ __forceinline__ void st_out(T *p, T v) {
 
 // quantize_row_q4_0 of one 32-block held one value per lane by a half-wave (lanes 0-31:
 // block A, 32-63: block B): returns the lane's code q (0..15) and the block's scale d.
-__device__ __forceinline__ int q4_half(float v, float &d) {
+// SEQNAN: the block may mix NaNs with other values (the GEMVs' GELU epilogue: the table gives NaN
+// for -inf and inf for +inf, beside finite neighbours), where the order of the reference's
+// amax = MAX(amax, fabsf(v)) = amax > |v| ? amax : |v| from 0 shows: a NaN replaces the running
+// maximum and the next element replaces the NaN, so amax is the maximum of the elements behind
+// the block's last NaN, or NaN when its last element is one (quantize_half then also packs the
+// codes as the reference does when they leave 0..15).  l: the lane's element, 0..31.  Without
+// it (rows that are NaN in every element or in none: a LayerNorm's, a head's) the tree's amax is
+// the reference's as it stands.
+template <bool SEQNAN = false>
+__device__ __forceinline__ int q4_half(float v, float &d, int l = 0) {
   // amax over the half-wave: DPP within rows of 16 lanes, then rows 0<->1 and 2<->3 by
   // ds_swizzle (xor 16); no LDS round trips in the dependent chain
   auto mx = [](float a, float b) { return a > b ? a : b; };
   float a = fabsf(v);
+  int last_nan = -1;
+  if constexpr (SEQNAN) {
+    const unsigned long long nm = __ballot(v != v);
+    last_nan = 31 - __clz((threadIdx.x & 32) ? (unsigned)(nm >> 32) : (unsigned)nm);  // -1: none
+    if (l <= last_nan) a = 0.0f;
+  }
   a = mx(a, dpp::mov<dpp::QP_XOR1, 0xF>(a, 0.0f));
   a = mx(a, dpp::mov<dpp::QP_XOR2, 0xF>(a, 0.0f));
   a = mx(a, dpp::mov<dpp::HALF_MIRROR, 0xF>(a, 0.0f));
   a = mx(a, dpp::mov<dpp::MIRROR, 0xF>(a, 0.0f));
   a = mx(a, __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(a), 0x401F)));
+  if (SEQNAN && last_nan == 31) a = __builtin_nanf("");
   d = a / 7.0f;
   const float id = d != 0.0f ? 1.0f / d : 0.0f;
   return x86_round_i8(v * id) + 8;
 }
 
-template <bool CO = false>
+template <bool CO = false, bool SEQNAN = false>
 __device__ __forceinline__ void quantize_half(float v, int lane, bool ok, uint8_t *qs_out, float *d_out,
                                               float *xd_out) {
   float d;
-  const int q = q4_half(v, d);
   const int l = lane & 31;
+  const int q = q4_half<SEQNAN>(v, d, l);
   // byte of pair l/2 (nibbles of lanes 2j, 2j+1), then OR of each 8-lane group's bytes into
   // its word: xor 1, xor 2, and the half-row mirror (lane i <-> 7-i) reach all 8 lanes
   const int qn = dpp::mov<dpp::QP_XOR1, 0xF>(q, 0);
-  const uint32_t byte = (l & 1) ? (uint32_t)((qn & 0xF) | ((q & 0xF) << 4)) : (uint32_t)((q & 0xF) | ((qn & 0xF) << 4));
+  uint32_t byte;
+  int qe = q;  // the code the reference dequantizes for this element
+  if constexpr (SEQNAN) {
+    // An element in front of the block's last NaN can exceed the amax behind it, and its code
+    // 0..15: the reference packs pp = vi0 | (vi1 << 4) from two uint8_t without a mask, so the
+    // even element's high bits land in the odd one's nibble, and multiplies with the stored nibbles
+    const uint32_t lo = (uint32_t)((l & 1) ? qn : q) & 0xFFu, hi = (uint32_t)((l & 1) ? q : qn) & 0xFFu;
+    byte = (lo | (hi << 4)) & 0xFFu;
+    qe = (int)((l & 1) ? byte >> 4 : byte & 0xFu);
+  } else {
+    byte = (l & 1) ? (uint32_t)((qn & 0xF) | ((q & 0xF) << 4)) : (uint32_t)((q & 0xF) | ((qn & 0xF) << 4));
+  }
   uint32_t word = byte << (8 * ((l >> 1) & 3));
   word |= (uint32_t)dpp::mov<dpp::QP_XOR2, 0xF>((int)word, 0);
   word |= (uint32_t)dpp::mov<dpp::HALF_MIRROR, 0xF>((int)word, 0);
   if (ok) {
     if ((l & 7) == 0) st_out<CO>((uint32_t *)qs_out + (l >> 3), word);
     if (l == 0) st_out<CO>(d_out, d);
-    st_out<CO>(xd_out + xd_slot(l), d * (float)(q - 8));
+    st_out<CO>(xd_out + xd_slot(l), d * (float)(qe - 8));
   }
 }
 

@@ -60,6 +60,7 @@ EXPORTS = [
     "vsim_op_tail_attn", "vsim_op_tail_ln", "vsim_op_tail_ln_ws_bytes",
     "vsim_op_w4a16_rows", "vsim_op_q4_gemm_w4a16_rows", "vsim_model_decode_batch_w4a16",
     "vsim_model_decode_batch_sample_w4a16",
+    "vsim_op_ln_quant", "vsim_op_gemv_batch",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -179,6 +180,27 @@ class TailLnArgs(ctypes.Structure):
                 ("b2", ctypes.c_void_p), ("jout", ctypes.c_void_p), ("q1", ctypes.c_void_p), ("xd1", ctypes.c_void_p),
                 ("q2", ctypes.c_void_p), ("xd2", ctypes.c_void_p), ("epoch", ctypes.c_uint32), ("il", ctypes.c_int32),
                 ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_size_t)]
+
+
+class LnQuantArgs(ctypes.Structure):
+    """vsim_ln_quant_args (include/vsim_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("n", ctypes.c_int32), ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p),
+                ("q1", ctypes.c_void_p), ("xd1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("q2", ctypes.c_void_p), ("xd2", ctypes.c_void_p), ("ja", ctypes.c_void_p), ("jab", ctypes.c_void_p),
+                ("jf", ctypes.c_void_p), ("jfb", ctypes.c_void_p), ("jout", ctypes.c_void_p),
+                ("epoch", ctypes.c_void_p)]
+
+
+class GemvBatchJob(ctypes.Structure):
+    """vsim_gemv_batch_job (include/vsim_hip.h)."""
+    _fields_ = [("w", ctypes.c_void_p), ("M", ctypes.c_int32), ("K", ctypes.c_int32), ("xd", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("y", ctypes.c_void_p), ("gelu_q", ctypes.c_int32),
+                ("oq", ctypes.c_void_p), ("oxd", ctypes.c_void_p)]
+
+
+class GemvBatchArgs(ctypes.Structure):
+    """vsim_gemv_batch_args (include/vsim_hip.h)."""
+    _fields_ = [("j", GemvBatchJob * 4), ("nj", ctypes.c_int32)]
 
 
 class QuantizeStats(ctypes.Structure):
@@ -322,6 +344,8 @@ def lib():
     L.vsim_op_q4_gemm_w4a16_rows.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
     L.vsim_model_decode_batch_w4a16.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.vsim_model_decode_batch_sample_w4a16.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(vp), vp]
+    L.vsim_op_ln_quant.argtypes = [ctypes.POINTER(LnQuantArgs), vp]
+    L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
     _lib = L
     return L
 
@@ -537,6 +561,36 @@ def tail_ln(args, stream=None):
     """vsim_op_tail_ln: the fused layer tail with its LayerNorm on the operands of `args`
     (tail_ln_args); waits for the stream."""
     check(lib().vsim_op_tail_ln(ctypes.byref(args), stream), "tail_ln")
+
+
+def ln_quant_args(x, n, w1, b1, q1, xd1, w2=None, b2=None, q2=None, xd2=None, ja=None, jab=None, jf=None, jfb=None,
+                  jout=None, epoch=None):
+    """vsim_ln_quant_args from torch tensors (or None)."""
+    return LnQuantArgs(ptr(x), int(n), ptr(w1), ptr(b1), ptr(q1), ptr(xd1), ptr(w2), ptr(b2), ptr(q2), ptr(xd2),
+                       ptr(ja), ptr(jab), ptr(jf), ptr(jfb), ptr(jout), ptr(epoch))
+
+
+def ln_quant(args, stream=None):
+    """vsim_op_ln_quant: k_ln_quant on the operands of `args` (ln_quant_args); stream-ordered."""
+    check(lib().vsim_op_ln_quant(ctypes.byref(args), stream), "ln_quant")
+
+
+def gemv_batch_args(jobs):
+    """vsim_gemv_batch_args from jobs = [(w, M, K, xd, bias, y, gelu_q, oq, oxd)], torch tensors or None."""
+    a = GemvBatchArgs()
+    a.nj = len(jobs)
+    for i, (w, M, K, xd, bias, y, gelu_q, oq, oxd) in enumerate(jobs[:4]):
+        a.j[i] = GemvBatchJob(ptr(w), int(M), int(K), ptr(xd), ptr(bias), ptr(y), int(gelu_q), ptr(oq), ptr(oxd))
+    return a
+
+
+def gemv_batch(jobs, stream=None) -> int:
+    """vsim_op_gemv_batch on jobs (gemv_batch_args); returns the kernel it chose: 1 k_gemv_solo, 0
+    k_gemv_chain32.  Stream-ordered."""
+    a = jobs if isinstance(jobs, GemvBatchArgs) else gemv_batch_args(jobs)
+    kern = ctypes.c_int32(-1)
+    check(lib().vsim_op_gemv_batch(ctypes.byref(a), ctypes.byref(kern), stream), "gemv_batch")
+    return int(kern.value)
 
 
 def fast_gemv(jobs, xq=(None, None), lnx=None, lnw=(None, None), lnb=(None, None), oq=None, n_past=None, cs=None,
