@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "decode_jobs.hpp"
 #include "fast.hpp"
 #include "graph.hpp"
 #include "../../include/vsim_hip.h"
@@ -28,6 +29,109 @@ using namespace vsim;
     int rc_ = (x);           \
     if (rc_) return rc_;     \
   } while (0)
+
+namespace {
+
+// ---- the exact decode step's kernels on caller buffers, their jobs built by decode_jobs.hpp as
+// model.cpp's enqueue_decode builds them.
+//
+// What a call allocates for itself, in one block: `head` bytes for the entry, then the RoPE table
+// built here on the host when the caller brought none (such a call waits for the stream before it
+// returns: the block is freed with this object).
+struct CallBuf {
+  uint8_t *buf = nullptr;
+  size_t head = 0;
+  std::vector<double2> cs;
+  ~CallBuf() {
+    if (buf) (void)hipFree(buf);
+  }
+  int alloc(size_t head_bytes, bool want_table, int n_pos, int n_rot) {
+    head = head_bytes;
+    if (want_table) {
+      cs.resize((size_t)n_pos * (n_rot / 2));
+      rope_table_host(cs.data(), n_pos, n_rot);
+    }
+    if (head + cs.size()) VSIM_HIP(hipMalloc(&buf, head + cs.size() * sizeof(double2)));
+    return VSIM_OK;
+  }
+  const double2 *table() const { return (const double2 *)(buf + head); }
+  bool upload_table(hipStream_t s) const {
+    return cs.empty() ||
+           hipMemcpyAsync(buf + head, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess;
+  }
+};
+// launch(table) behind the upload of a table built here; waits for the stream
+template <class Launch>
+int with_rope_table(int n_pos, int n_rot, hipStream_t s, Launch launch) {
+  CallBuf own;
+  RC(own.alloc(0, true, n_pos, n_rot));
+  int rc = own.upload_table(s) ? launch(own.table()) : VSIM_EHIP;
+  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = VSIM_EHIP;
+  return rc;
+}
+
+// The attention of a vsim_attn_batch_args (its RoPE and exp tables apart, which a call may have to
+// make first); false when an argument fails the checks that every attention entry makes.
+bool attn_desc(const vsim_attn_batch_args *a, int nsplit, AttnDesc *D) {
+  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->d <= 0 ||
+      a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2)
+    return false;
+  *D = AttnDesc{.d = a->d, .H = a->H, .n_rot = a->n_rot, .style = a->style, .n_ctx = a->n_ctx, .nsplit = nsplit,
+                .kqv_nth = a->kqv_nth, .scale = a->scale, .alibi = a->alibi, .q = a->q, .k = a->k, .v = a->v,
+                .cs = (const double2 *)a->cs, .o = {q4_rows(a->oq, a->d * a->H, a->B > 0 ? a->B : 0), a->oxd},
+                .out = a->out};
+  return true;
+}
+
+// One k_layer_tail launch on the call's operands, for vsim_op_tail_attn and vsim_op_tail_ln: the
+// call's own block (the tail workspace for width ws_E unless the caller brought one, zeroed; the RoPE
+// table unless the caller brought one), the epoch word, the cache pointers read back, launch(A, W)
+// under the tag of (epoch, il), then every head part's flag checked against that tag and, with
+// check_spin, the bounded waits' counter against its value before the launch.  A caller's
+// workspace is written at its epoch word only (stale granules stay where they are).
+template <class Launch>
+int tail_call(const char *who, const vsim_attn_batch_args *a, AttnDesc D, void *caller_ws, int ws_E, unsigned epoch,
+              int il, bool check_spin, hipStream_t s, Launch launch) {
+  DevTables tab;
+  RC(tables_get(&tab));
+  const int na = a->H * D.nsplit;
+  CallBuf own;
+  RC(own.alloc(caller_ws ? 0 : tail_ws_bytes(ws_E), !a->cs && a->n_rot > 0, a->n_ctx, a->n_rot));
+  const TailWs W = tail_ws_carve(caller_ws ? caller_ws : own.buf, ws_E);
+  const unsigned tag = (epoch << 8) | (unsigned)(il + 1);
+  unsigned *spin = check_spin ? spin_error_counter() : nullptr;
+  unsigned spin0 = 0, spin1 = 0;
+  float *kc = nullptr, *vc = nullptr;
+  std::vector<unsigned long long> flags(na);
+  if ((own.head && hipMemsetAsync(own.buf, 0, own.head, s) != hipSuccess) ||
+      hipMemcpyAsync(W.ep, &epoch, sizeof(epoch), hipMemcpyHostToDevice, s) != hipSuccess || !own.upload_table(s) ||
+      hipMemcpyAsync(&kc, a->kc, sizeof(kc), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(&vc, a->vc, sizeof(vc), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      (spin && hipMemcpyAsync(&spin0, spin, sizeof(spin0), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return VSIM_EHIP;
+  if (!kc || !vc) return VSIM_EINVAL;
+  if (!a->cs) D.cs = own.table();
+  D.etab = tab.exp_f16;
+  RC(launch(attn_job(D, kc, vc, a->n_past), W));
+  if (hipMemcpyAsync(flags.data(), W.hflag, na * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      (spin && hipMemcpyAsync(&spin1, spin, sizeof(spin1), hipMemcpyDeviceToHost, s) != hipSuccess) ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return VSIM_EHIP;
+  int rc = VSIM_OK;
+  for (int i = 0; i < na; ++i)
+    if ((unsigned)(flags[i] >> 32) != tag) {
+      set_error(std::string(who) + ": a head part did not raise its flag");
+      rc = VSIM_EHIP;
+    }
+  if (spin1 != spin0) {
+    set_error(std::string(who) + ": a bounded wait inside the layer tail gave up");
+    rc = VSIM_ESPIN;
+  }
+  return rc;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -86,140 +190,49 @@ int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, con
 int vsim_batch_set_gemm(int enable) { return batch_set_gemm(enable); }
 int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->d <= 0 ||
-      a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2) {
+  AttnDesc D;
+  if (!attn_desc(a, 1, &D)) {
     set_error("attn_decode_batch: bad argument");
     return VSIM_EINVAL;
   }
   DevTables tab;
   RC(tables_get(&tab));
-  if (a->n_rot > 0 && !a->cs) {  // the table built here, as vsim_op_rope does: this call then waits
-    std::vector<double2> cs((size_t)a->n_ctx * (a->n_rot / 2));
-    rope_table_host(cs.data(), a->n_ctx, a->n_rot);
-    double2 *dcs = nullptr;
-    VSIM_HIP(hipMalloc(&dcs, cs.size() * sizeof(double2)));
-    vsim_attn_batch_args b = *a;
-    b.cs = (const double *)dcs;
-    hipStream_t s = (hipStream_t)stream;
-    int rc = hipMemcpyAsync(dcs, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess
-                 ? vsim_op_attn_decode_batch(&b, stream)
-                 : VSIM_EHIP;
-    if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = VSIM_EHIP;
-    (void)hipFree(dcs);
-    return rc;
-  }
-  const size_t nblk = (size_t)(a->B > 0 ? a->B : 0) * (a->d * a->H / QK);
-  AttnJob A{};
-  A.q = a->q;
-  A.k = a->k;
-  A.v = a->v;
-  A.cs = (const double2 *)a->cs;
-  A.etab = tab.exp_f16;
-  A.d = a->d;
-  A.H = a->H;
-  A.n_rot = a->n_rot;
-  A.style = a->style;
-  A.n_ctx = a->n_ctx;
-  A.nsplit = 1;
-  A.kqv_nth = a->kqv_nth;
-  A.scale = a->scale;
-  A.alibi = a->alibi;
-  A.oq_qs = (uint8_t *)a->oq;
-  A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
-  A.oxd = a->oxd;
-  A.out = a->out;
+  D.etab = tab.exp_f16;
+  hipStream_t s = (hipStream_t)stream;
   const AttnRows R{a->kc, a->vc, 0, a->n_past};
-  return launch_attn_decode_batch(A, R, a->B, a->n_ctx, (hipStream_t)stream);
+  auto launch = [&](const double2 *cs) {
+    D.cs = cs;
+    return launch_attn_decode_batch(attn_job(D, nullptr, nullptr, nullptr), R, a->B, a->n_ctx, s);
+  };
+  return a->n_rot > 0 && !a->cs ? with_rope_table(a->n_ctx, a->n_rot, s, launch) : launch(D.cs);
 }
+
 // The heads of k_layer_tail alone (attn_body<704, true>: 11 waves, write-through stores, nsplit
 // workgroups per head): launch_layer_tail with neither an fc_out nor an out-projection job, so
-// every workgroup takes the head role, on a flag buffer and an epoch word of the call's own.
+// every workgroup takes the head role, on flags and an epoch word of the call's own (epoch 1, layer 0).
 int vsim_op_tail_attn(const vsim_attn_batch_args *a, int nsplit, void *stream) {
-  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->B != 1 ||
-      a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || nsplit < 1 ||
-      nsplit > 2 || (long long)a->H * nsplit > TAIL_MAX_HEADS) {
+  AttnDesc D;
+  if (!attn_desc(a, nsplit, &D) || a->B != 1 || nsplit < 1 || nsplit > 2 ||
+      (long long)a->H * nsplit > TAIL_MAX_HEADS) {
     set_error("tail_attn: bad argument (one row, nsplit 1 or 2, at most 128 head parts)");
     return VSIM_EINVAL;
   }
   hipStream_t s = (hipStream_t)stream;
-  DevTables tab;
-  RC(tables_get(&tab));
-  const int half = a->n_rot / 2, na = a->H * nsplit;
-  // one allocation: the epoch word, the heads' flags (8-byte granules), the RoPE table if built here
-  const size_t cs_off = 256 + (size_t)TAIL_MAX_HEADS * sizeof(unsigned long long);
-  const size_t cs_n = a->cs ? 0 : (size_t)a->n_ctx * half;
-  uint8_t *buf = nullptr;
-  VSIM_HIP(hipMalloc(&buf, cs_off + cs_n * sizeof(double2)));
-  unsigned *ep = (unsigned *)buf;
-  unsigned long long *hflag = (unsigned long long *)(buf + 256);
-  std::vector<double2> cs(cs_n);
-  if (cs_n) rope_table_host(cs.data(), a->n_ctx, a->n_rot);
-  const unsigned epoch = 1;
-  float *kc = nullptr, *vc = nullptr;
-  std::vector<unsigned long long> flags(na);
-  int rc = VSIM_EHIP;
-  if (hipMemsetAsync(buf, 0, cs_off, s) == hipSuccess &&
-      hipMemcpyAsync(ep, &epoch, sizeof(epoch), hipMemcpyHostToDevice, s) == hipSuccess &&
-      (!cs_n || hipMemcpyAsync(buf + cs_off, cs.data(), cs_n * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess) &&
-      hipMemcpyAsync(&kc, a->kc, sizeof(kc), hipMemcpyDeviceToHost, s) == hipSuccess &&
-      hipMemcpyAsync(&vc, a->vc, sizeof(vc), hipMemcpyDeviceToHost, s) == hipSuccess &&
-      hipStreamSynchronize(s) == hipSuccess) {
-    const size_t nblk = (size_t)(a->d * a->H / QK);
-    AttnJob A{};
-    A.q = a->q;
-    A.k = a->k;
-    A.v = a->v;
-    A.kc = kc;
-    A.vc = vc;
-    A.npast = a->n_past;
-    A.cs = a->cs ? (const double2 *)a->cs : (const double2 *)(buf + cs_off);
-    A.etab = tab.exp_f16;
-    A.d = a->d;
-    A.H = a->H;
-    A.n_rot = a->n_rot;
-    A.style = a->style;
-    A.n_ctx = a->n_ctx;
-    A.nsplit = nsplit;
-    A.kqv_nth = a->kqv_nth;
-    A.scale = a->scale;
-    A.alibi = a->alibi;
-    A.oq_qs = (uint8_t *)a->oq;
-    A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
-    A.oxd = a->oxd;
-    A.out = a->out;
+  return tail_call("tail_attn", a, D, nullptr, 0, 1, 0, false, s, [&](const AttnJob &A, const TailWs &W) {
     const GemvBatch none{};
-    rc = kc && vc ? launch_layer_tail(none, none, A, TailSync{hflag, ep, 0}, a->n_ctx, s) : VSIM_EINVAL;
-    if (rc == VSIM_OK) {
-      // every head part must have raised its flag with this call's tag (epoch << 8 | layer + 1)
-      if (hipMemcpyAsync(flags.data(), hflag, na * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-          hipStreamSynchronize(s) != hipSuccess) {
-        rc = VSIM_EHIP;
-      } else {
-        for (int i = 0; i < na; ++i)
-          if ((unsigned)(flags[i] >> 32) != ((epoch << 8) | 1u)) {
-            set_error("tail_attn: a head part did not raise its flag");
-            rc = VSIM_EHIP;
-          }
-      }
-    }
-  }
-  (void)hipFree(buf);
-  return rc;
+    return launch_layer_tail(none, none, A, TailSync{W.hflag, W.ep, 0}, a->n_ctx, s);
+  });
 }
 // The whole k_layer_tail with its LayerNorm (TailJob::ln): launch_layer_tail(Bf, Bo, A, sy, n_ctx, s, &N)
-// on the call's operands.  Workspace (the caller's, or one of the call's own, zeroed): the epoch
-// word (own 256-byte line), og [E], jg [E], rec [2 E/32], the heads' flags -- the executor's block.
-static size_t tail_ln_ws_bytes(size_t E) {
-  return 256 + 2 * E * sizeof(unsigned long long) + 2 * (E / QK) * sizeof(uint4) +
-         (size_t)TAIL_MAX_HEADS * sizeof(unsigned long long);
-}
-size_t vsim_op_tail_ln_ws_bytes(int E) { return E > 0 && E % QK == 0 ? tail_ln_ws_bytes((size_t)E) : 0; }
+// on the call's operands, over the caller's workspace or one of the call's own (decode_jobs.hpp's
+// TailWs, the block the executor allocates).
+size_t vsim_op_tail_ln_ws_bytes(int E) { return E > 0 && E % QK == 0 ? tail_ws_bytes((size_t)E) : 0; }
 int vsim_op_tail_ln(const vsim_tail_ln_args *t, void *stream) {
   const vsim_attn_batch_args *a = t ? &t->attn : nullptr;
-  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->oq || !a->oxd || a->B != 1 ||
-      a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || t->nsplit < 1 ||
-      t->nsplit > 2 || (long long)a->H * t->nsplit > TAIL_MAX_HEADS || (long long)a->d * a->H > LNT_MAX_TILES * T32 ||
-      a->d % QK || a->d > 256 || a->d % t->nsplit || (a->d / t->nsplit) % QK) {
+  AttnDesc D;
+  if (!attn_desc(a, t ? t->nsplit : 0, &D) || a->B != 1 || t->nsplit < 1 || t->nsplit > 2 ||
+      (long long)a->H * t->nsplit > TAIL_MAX_HEADS || (long long)a->d * a->H > LNT_MAX_TILES * T32 || a->d % QK ||
+      a->d > 256 || a->d % t->nsplit || (a->d / t->nsplit) % QK) {
     set_error("tail_ln: bad attention row (one row, d % 32 == 0, d <= 256, nsplit 1 or 2 with whole 32-blocks per "
               "part, at most 128 head parts, E <= 8192)");
     return VSIM_EINVAL;
@@ -239,7 +252,7 @@ int vsim_op_tail_ln(const vsim_tail_ln_args *t, void *stream) {
     set_error("tail_ln: the layer index of the tag is 0..254");
     return VSIM_EINVAL;
   }
-  if (t->ws && (t->ws_bytes < tail_ln_ws_bytes(E) || ((uintptr_t)t->ws & 255))) {
+  if (t->ws && (t->ws_bytes < tail_ws_bytes(E) || ((uintptr_t)t->ws & 255))) {
     set_error("tail_ln: the workspace is vsim_op_tail_ln_ws_bytes(E) bytes, 256-byte aligned");
     return VSIM_EINVAL;
   }
@@ -248,115 +261,17 @@ int vsim_op_tail_ln(const vsim_tail_ln_args *t, void *stream) {
     return VSIM_EINVAL;
   }
   hipStream_t s = (hipStream_t)stream;
-  DevTables tab;
-  RC(tables_get(&tab));
-  const int half = a->n_rot / 2, na = a->H * t->nsplit;
-  // one allocation of the call's own: the workspace unless the caller brought one, the RoPE table if built here
-  const size_t ws_n = t->ws ? 0 : tail_ln_ws_bytes(E);
-  const size_t cs_n = a->cs ? 0 : (size_t)a->n_ctx * half;
-  uint8_t *buf = nullptr;
-  if (ws_n + cs_n) VSIM_HIP(hipMalloc(&buf, ws_n + cs_n * sizeof(double2)));
-  uint8_t *ws = t->ws ? (uint8_t *)t->ws : buf;
-  unsigned *ep = (unsigned *)ws;
-  unsigned long long *og = (unsigned long long *)(ws + 256), *jg = og + E;
-  uint4 *rec = (uint4 *)(jg + E);
-  unsigned long long *hflag = (unsigned long long *)(rec + 2 * (E / QK));
-  std::vector<double2> cs(cs_n);
-  if (cs_n) rope_table_host(cs.data(), a->n_ctx, a->n_rot);
-  const unsigned epoch = t->epoch, tag = (epoch << 8) | (unsigned)(t->il + 1);
-  unsigned *spin = spin_error_counter();
-  unsigned spin0 = 0, spin1 = 0;
-  float *kc = nullptr, *vc = nullptr;
-  std::vector<unsigned long long> flags(na);
-  int rc = VSIM_EHIP;
-  if ((!ws_n || hipMemsetAsync(buf, 0, ws_n, s) == hipSuccess) &&
-      hipMemcpyAsync(ep, &epoch, sizeof(epoch), hipMemcpyHostToDevice, s) == hipSuccess &&
-      (!cs_n || hipMemcpyAsync(buf + ws_n, cs.data(), cs_n * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess) &&
-      hipMemcpyAsync(&kc, a->kc, sizeof(kc), hipMemcpyDeviceToHost, s) == hipSuccess &&
-      hipMemcpyAsync(&vc, a->vc, sizeof(vc), hipMemcpyDeviceToHost, s) == hipSuccess &&
-      (!spin || hipMemcpyAsync(&spin0, spin, sizeof(spin0), hipMemcpyDeviceToHost, s) == hipSuccess) &&
-      hipStreamSynchronize(s) == hipSuccess) {
-    const size_t nblk = (size_t)(E / QK);
-    AttnJob A{};
-    A.q = a->q;
-    A.k = a->k;
-    A.v = a->v;
-    A.kc = kc;
-    A.vc = vc;
-    A.npast = a->n_past;
-    A.cs = a->cs ? (const double2 *)a->cs : (const double2 *)(buf + ws_n);
-    A.etab = tab.exp_f16;
-    A.d = a->d;
-    A.H = a->H;
-    A.n_rot = a->n_rot;
-    A.style = a->style;
-    A.n_ctx = a->n_ctx;
-    A.nsplit = t->nsplit;
-    A.kqv_nth = a->kqv_nth;
-    A.scale = a->scale;
-    A.alibi = a->alibi;
-    A.oq_qs = (uint8_t *)a->oq;
-    A.oq_d = (float *)((uint8_t *)a->oq + nblk * 16);
-    A.oxd = a->oxd;
-    A.out = a->out;
-    GemvBatch Bf{}, Bo{};
-    Bf.nj = Bo.nj = 1;
-    Bf.j[0].w = w4_view(t->wf, E, t->K);  // fc_out on the caller's factors
-    Bf.j[0].xd = t->xd;
-    Bf.j[0].epi = EPI_STORE;
-    Bo.j[0].w = w4_view(t->wo, E, E);  // the out-projection on the heads' output
-    Bo.j[0].xd = a->oxd;
-    Bo.j[0].xqs = A.oq_qs;
-    Bo.j[0].xdd = A.oq_d;
-    Bo.j[0].epi = EPI_STORE;
-    TailLn N{};
-    N.x = t->x;
-    N.ab = t->ab;
-    N.fb = t->fb;
-    N.jout = t->jout;
-    N.w1 = t->w1;
-    N.b1 = t->b1;
-    N.q1 = (uint8_t *)t->q1;
-    N.d1 = (float *)((uint8_t *)t->q1 + nblk * 16);
-    N.xd1 = t->xd1;
-    if (two) {
-      N.w2 = t->w2;
-      N.b2 = t->b2;
-      N.q2 = (uint8_t *)t->q2;
-      N.d2 = (float *)((uint8_t *)t->q2 + nblk * 16);
-      N.xd2 = t->xd2;
-    }
-    N.og = og;
-    N.jg = jg;
-    N.rec = rec;
-    N.ep = ep;
-    N.stats = dev_stats();
-    N.il = t->il;
-    rc = kc && vc ? launch_layer_tail(Bf, Bo, A, TailSync{hflag, ep, t->il}, a->n_ctx, s, &N) : VSIM_EINVAL;
-    if (rc == VSIM_OK) {
-      // every head part must have raised its flag with this call's tag, and no bounded wait may have given up
-      if (hipMemcpyAsync(flags.data(), hflag, na * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) != hipSuccess ||
-          (spin && hipMemcpyAsync(&spin1, spin, sizeof(spin1), hipMemcpyDeviceToHost, s) != hipSuccess) ||
-          hipStreamSynchronize(s) != hipSuccess) {
-        rc = VSIM_EHIP;
-      } else {
-        for (int i = 0; i < na; ++i)
-          if ((unsigned)(flags[i] >> 32) != tag) {
-            set_error("tail_ln: a head part did not raise its flag");
-            rc = VSIM_EHIP;
-          }
-        if (spin1 != spin0) {
-          set_error("tail_ln: a bounded wait inside the layer tail gave up");
-          rc = VSIM_ESPIN;
-        }
-      }
-    }
-  }
-  if (buf) (void)hipFree(buf);
-  return rc;
+  return tail_call("tail_ln", a, D, t->ws, E, t->epoch, t->il, true, s, [&](const AttnJob &A, const TailWs &W) {
+    // fc_out on the caller's factors, the out-projection on the heads' output
+    const GemvBatch Bf = gemv_batch({gemv_job(t->wf, E, t->K, t->xd, Q4Rows{}, nullptr, nullptr)});
+    const GemvBatch Bo = gemv_batch({gemv_job(t->wo, E, E, D.o, nullptr, nullptr)});
+    const NormRow n1{t->w1, t->b1, {q4_rows(t->q1, E), t->xd1}}, n2{t->w2, t->b2, {q4_rows(t->q2, E), t->xd2}};
+    const TailLn N = tail_ln_job(t->x, t->jout, t->ab, t->fb, n1, two ? &n2 : nullptr, W, dev_stats(), t->il);
+    return launch_layer_tail(Bf, Bo, A, TailSync{W.hflag, W.ep, t->il}, a->n_ctx, s, &N);
+  });
 }
-// k_ln_quant on the call's operands: launch_ln_quant(j1, two ? &j2 : nullptr, n, s), the second
-// job joining the same operands without storing them (model.cpp's join_into(j2, false)).
+// k_ln_quant on the call's operands: launch_ln_quant on decode_jobs.hpp's ln_quant_jobs, the second
+// job joining the same operands without storing them.
 int vsim_op_ln_quant(const vsim_ln_quant_args *a, void *stream) {
   // the row in dynamic LDS beside ln_exact_lds_t's static words, within the 64 KB a launch gets unasked
   constexpr int LNQ_MAX_N = (65536 - 256) / 4 / QK * QK;
@@ -400,29 +315,14 @@ int vsim_op_ln_quant(const vsim_ln_quant_args *a, void *stream) {
   }
   DevTables tab;
   RC(tables_get(&tab));  // (the device's fallback counters come with its tables)
-  const size_t nblk = (size_t)(a->n / QK);
-  LnQuantJob j1{a->x, a->w1, a->b1, (uint8_t *)a->q1, (float *)((uint8_t *)a->q1 + nblk * 16), a->xd1};
-  j1.ja = a->ja;
-  j1.jab = a->jab;
-  j1.jf = a->jf;
-  j1.jfb = a->jfb;
-  LnQuantJob j2 = j1;  // the same row and join, no jout, no epoch
-  j1.jout = a->jout;
-  j1.ep = a->epoch;
-  if (two) {
-    j2.w = a->w2;
-    j2.b = a->b2;
-    j2.qs = (uint8_t *)a->q2;
-    j2.d = (float *)((uint8_t *)a->q2 + nblk * 16);
-    j2.xd = a->xd2;
-  }
-  return launch_ln_quant(j1, two ? &j2 : nullptr, a->n, (hipStream_t)stream);
+  const NormRow n1{a->w1, a->b1, {q4_rows(a->q1, a->n), a->xd1}}, n2{a->w2, a->b2, {q4_rows(a->q2, a->n), a->xd2}};
+  const LnJoin join{a->ja, a->jab, a->jf, a->jfb, a->jout};
+  const LnQuantPair P = ln_quant_jobs(a->x, n1, two ? &n2 : nullptr, &join, a->epoch);
+  return launch_ln_quant(P.j1, P.second(), a->n, (hipStream_t)stream);
 }
 // launch_gemv_chain_batch (k_gemv_solo or k_gemv_chain32, as gemv_chain_solo decides) on the call's jobs.
 int vsim_op_gemv_batch(const vsim_gemv_batch_args *a, int32_t *kernel, void *stream) {
   if (!a || a->nj < 1 || a->nj > 4) { set_error("gemv_batch: 1 to 4 jobs"); return VSIM_EINVAL; }
-  GemvBatch B{};
-  B.nj = a->nj;
   bool gelu = false;
   for (int i = 0; i < a->nj; ++i) {
     const vsim_gemv_batch_job &j = a->j[i];
@@ -437,24 +337,16 @@ int vsim_op_gemv_batch(const vsim_gemv_batch_args *a, int32_t *kernel, void *str
       set_error("gemv_batch: w and xd must be 16-byte aligned, bias, y, oq and oxd 4-byte aligned");
       return VSIM_EINVAL;
     }
-    GemvJob &J = B.j[i];
-    J.w = w4_view(j.w, j.M, j.K);
-    J.xd = j.xd;
-    J.bias = j.bias;
-    J.y = j.y;
-    J.epi = j.gelu_q ? EPI_GELU_Q : EPI_STORE;
-    if (j.gelu_q) {
-      J.oq_qs = (uint8_t *)j.oq;
-      J.oq_d = (float *)((uint8_t *)j.oq + (size_t)(j.M / QK) * 16);
-      J.oxd = j.oxd;
-      gelu = true;
-    }
+    gelu |= j.gelu_q != 0;
   }
-  if (gelu) {
-    DevTables tab;
-    RC(tables_get(&tab));
-    for (int i = 0; i < a->nj; ++i)
-      if (B.j[i].epi == EPI_GELU_Q) B.j[i].gelu_tab = tab.gelu_f16;
+  DevTables tab{};
+  if (gelu) RC(tables_get(&tab));
+  GemvBatch B{};
+  B.nj = a->nj;
+  for (int i = 0; i < a->nj; ++i) {
+    const vsim_gemv_batch_job &j = a->j[i];
+    B.j[i] = gemv_job(j.w, j.M, j.K, j.xd, Q4Rows{}, j.bias, j.y);
+    if (j.gelu_q) gelu_quant_into(B.j[i], tab.gelu_f16, ActRow{q4_rows(j.oq, j.M), j.oxd});
   }
   if (kernel) *kernel = gemv_chain_solo(B) ? 1 : 0;
   return launch_gemv_chain_batch(B, (hipStream_t)stream);
@@ -606,17 +498,10 @@ int vsim_op_attn_softmax(float *p, int nc, int nr, int nz, int n_past, float sca
 int vsim_op_rope(int style, float *x, int d, int H, int T, int n_past, int n_dims, int mode, void *stream) {
   if (n_dims <= 0 || n_dims % 2 || n_dims > d) { set_error("rope: bad n_dims"); return VSIM_EINVAL; }
   const int n_pos = (mode == 0 ? n_past + T : T);
-  std::vector<double2> cs((size_t)n_pos * (n_dims / 2));
-  rope_table_host(cs.data(), n_pos, n_dims);
-  double2 *dcs = nullptr;
-  VSIM_HIP(hipMalloc(&dcs, cs.size() * sizeof(double2)));
   hipStream_t s = (hipStream_t)stream;
-  int rc = hipMemcpyAsync(dcs, cs.data(), cs.size() * sizeof(double2), hipMemcpyHostToDevice, s) == hipSuccess
-               ? launch_rope(style, x, d, H, T, n_past, n_dims, mode, dcs, s)
-               : VSIM_EHIP;
-  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) rc = VSIM_EHIP;
-  (void)hipFree(dcs);
-  return rc;
+  return with_rope_table(n_pos, n_dims, s, [&](const double2 *cs) {
+    return launch_rope(style, x, d, H, T, n_past, n_dims, mode, cs, s);
+  });
 }
 int vsim_op_kq(const float *K, int ldk, const float *Q, int ldq, int d, int H, int nk, int n, float *kq, void *stream) {
   return launch_kq(K, ldk, Q, ldq, d, H, nk, n, kq, (hipStream_t)stream);
@@ -685,8 +570,6 @@ int vsim_op_gemm_q4_256_h16(const void *w, int M, int K, const void *x16, int n,
 // check the shapes the kernels stage in LDS; the checks here are the ones the model's own
 // shapes make unnecessary (null operands, whole tiles where a kernel writes all 32 rows).
 static_assert(FD_PAD == VSIM_FAST_PAD, "include/vsim_hip.h states the weight slack");
-static inline const uint8_t *soa_qs(const void *xq) { return (const uint8_t *)xq; }
-static inline float *soa_d(const void *xq, int k) { return (float *)((uint8_t *)xq + (size_t)(k / QK) * 16); }
 
 int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
   if (!a || a->nj < 1 || a->nj > 4) { set_error("fast_gemv: 1 to 4 jobs"); return VSIM_EINVAL; }
@@ -707,8 +590,8 @@ int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
     rope |= j.epi == FE_ROPE_Q || j.epi == FE_ROPE_K;
     pos |= j.epi >= FE_ROPE_Q;
     if (j.epi == FE_GELU_Q) {
-      P.oq_qs = (uint8_t *)a->oq;
-      P.oq_d = soa_d(a->oq, j.rows);
+      P.oq_qs = q4_rows(a->oq, j.rows).qs;
+      P.oq_d = q4_rows(a->oq, j.rows).d;
     }
     P.j[i] = FastJob{w4_view(j.w, j.rows, j.k), j.bias, j.y, j.epi, j.act};
   }
@@ -720,8 +603,9 @@ int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
   }
   if (a->clear && a->nclear < 0) { set_error("fast_gemv: nclear < 0"); return VSIM_EINVAL; }
   for (int i = 0; i < 2; ++i) {
-    P.xq[i] = a->lnx ? nullptr : soa_qs(a->xq[i]);
-    P.xd[i] = a->lnx || !a->xq[i] ? nullptr : soa_d(a->xq[i], K);
+    const Q4Rows x = a->lnx || !a->xq[i] ? Q4Rows{} : q4_rows(a->xq[i], K);
+    P.xq[i] = x.qs;
+    P.xd[i] = x.d;
     P.lnw[i] = a->lnw[i];
     P.lnb[i] = a->lnb[i];
   }
@@ -751,8 +635,8 @@ int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream) {
   }
   FastTail T{};
   T.wf = w4_view(a->wf, a->rows, a->k);
-  T.xf_qs = soa_qs(a->xf);
-  T.xf_d = soa_d(a->xf, a->k);
+  T.xf_qs = q4_rows(a->xf, a->k).qs;
+  T.xf_d = q4_rows(a->xf, a->k).d;
   T.ffp = a->ffp;
   T.sf = a->sf;
   T.q = a->q;
@@ -765,8 +649,8 @@ int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream) {
   T.scale = a->scale;
   T.part = a->part;
   T.hcnt = a->hcnt;
-  T.oq_qs = (uint8_t *)a->oq;
-  T.oq_d = soa_d(a->oq, a->d * a->H);
+  T.oq_qs = q4_rows(a->oq, a->d * a->H).qs;
+  T.oq_d = q4_rows(a->oq, a->d * a->H).d;
   // the per-head counters are this call's (the model zeroes them from the layer's GEMV launch)
   VSIM_HIP(hipMemsetAsync(a->hcnt, 0, (size_t)4 * a->H * sizeof(unsigned), (hipStream_t)stream));
   return launch_fast_tail(T, (hipStream_t)stream);
@@ -780,8 +664,8 @@ int vsim_op_fast_oproj_join(const void *w, int E, const void *xq, const float *b
   }
   FastOproj O{};
   O.w = w4_view(w, E, E);
-  O.xq = soa_qs(xq);
-  O.xd = soa_d(xq, E);
+  O.xq = q4_rows(xq, E).qs;
+  O.xd = q4_rows(xq, E).d;
   O.bo = bo;
   O.ffp = ffp;
   O.sf = sf;

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "decode_jobs.hpp"
 #include "fast.hpp"
 #include "sampler.hpp"
 #include "../../include/vsim_hip.h"
@@ -162,12 +163,10 @@ struct vsim_model {
   int32_t *st_tok_out = nullptr;
   int st_npast = -1;
   unsigned *tail_done = nullptr;  // the fast decode step's per-head counters (fast_decode.hip)
-  // the tail LayerNorm's hand-off buffers (TailLn): the step epoch, the out-projection's and the joined row's
-  // granules [E], the per-tile partial sums [2 E/32]; zeroed at allocation (tag 0 never matches)
-  unsigned *lnt_ep = nullptr;
-  unsigned long long *lnt_og = nullptr, *lnt_jg = nullptr;
-  uint4 *lnt_rec = nullptr;
-  unsigned long long *tail_hflag = nullptr;  // the tail heads' flags (TailSync), in the same allocation
+  // the layer tail's hand-off block (TailSync, TailLn) and its views (decode_jobs.hpp: tail_ws_bytes,
+  // tail_ws_carve, null with it); zeroed at allocation (tag 0 never matches)
+  void *tail_ws = nullptr;
+  TailWs tw;
   // fast-mode decode step (fast_decode.hip): fc_out split-K partial rows and attention
   // chunk partials (both consumed by the layer's k_fast_oproj_join)
   float *fast_ffp = nullptr, *fast_part = nullptr;
@@ -245,21 +244,6 @@ struct ScratchBuf {
   int flags;
 };
 
-// The tail LayerNorm's block, one allocation at lnt_ep: epoch (own 256-byte line), og [E],
-// jg [E], rec [2 E/32], the heads' flags.  carve_lnt points the views into it (null with it).
-size_t lnt_bytes(size_t E) {
-  return 256 + 2 * E * sizeof(unsigned long long) + 2 * (E / QK) * sizeof(uint4) +
-         TAIL_MAX_HEADS * sizeof(unsigned long long);
-}
-void carve_lnt(vsim_model *m) {
-  const size_t E = E_(m);
-  uint8_t *p = (uint8_t *)m->lnt_ep;
-  m->lnt_og = p ? (unsigned long long *)(p + 256) : nullptr;
-  m->lnt_jg = p ? m->lnt_og + E : nullptr;
-  m->lnt_rec = p ? (uint4 *)(m->lnt_jg + E) : nullptr;
-  m->tail_hflag = p ? (unsigned long long *)(m->lnt_rec + 2 * (E / QK)) : nullptr;
-}
-
 std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   const size_t E = E_(m), F = 4 * E, V = m->hp.n_vocab, H = m->hp.n_head, f = sizeof(float);
   const size_t d = E / H, nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
@@ -300,7 +284,7 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->so_host, sizeof(TopkOut), S_PINNED);
   add(&m->tk_ws, TOPK_WS_BYTES, S_ZERO);
   add(&m->tail_done, ncnt * sizeof(unsigned), S_ZERO);
-  add(&m->lnt_ep, lnt_bytes(E), S_ZERO);  // one allocation, carved by carve_lnt
+  add(&m->tail_ws, tail_ws_bytes(E), S_ZERO);  // one allocation, its views in m->tw
   add(&m->fast_ffp, 8 * E * f);
   add(&m->pf_x16, n >= (size_t)GEMM_MIN_N ? n * (E + F) * sizeof(uint16_t) : 0, S_POISON);
   add(&m->fast_part, H * nch * (d + 2) * f, S_ZERO);  // finite stale values
@@ -331,7 +315,7 @@ void free_scratch(vsim_model *m) {
     if (*b.p) (void)(b.flags & S_PINNED ? hipHostFree(*b.p) : hipFree(*b.p));
     *b.p = nullptr;
   }
-  carve_lnt(m);
+  m->tw = tail_ws_carve(m->tail_ws, E_(m));
   if (m->pf_scratch) (void)hipFree(m->pf_scratch);
   m->pf_scratch = nullptr;
   m->pf_bytes = 0;
@@ -352,7 +336,7 @@ int ensure_scratch(vsim_model *m, int N) {
       VSIM_HIP(hipMalloc(b.p, b.bytes));
     if (b.flags & S_ZERO) VSIM_HIP(hipMemset(*b.p, 0, b.bytes));
   }
-  carve_lnt(m);
+  m->tw = tail_ws_carve(m->tail_ws, E_(m));
   m->n_max = n;
   return VSIM_OK;
 }
@@ -393,9 +377,6 @@ int ensure_pf_scratch(vsim_model *m) {
   VSIM_HIP(hipMalloc(&m->pf_scratch, m->pf_bytes));
   return VSIM_OK;
 }
-
-// the scales of a Q4 SoA activation row of k values: they follow its 16-byte quants
-float *q4_scales(uint8_t *q, int k) { return (float *)(q + (size_t)(k / QK) * 16); }
 
 // ---------------------------------------------------------------- tensors
 // One row per tensor of an architecture: where its device pointer lives (a LayerW member, or
@@ -648,36 +629,17 @@ int prof_collect(vsim_model *m) {
 double w4_algo_bytes(const W4 &w) { return (double)w.rows * w.k / QK * QBYTES; }
 
 // The heads of one decode step's layer (attn.hpp) on this layer's Q / K / V rows in Qb / Kb / Vb:
-// the attention output leaves quantized in oq_qs / oq_d with its factors in oxd, every head over
-// nsplit workgroups.  kc / vc / npast: the layer's cache and the device position of the
-// single-token step; null for a rows batch, whose rows each have their own (AttnRows).
-AttnJob decode_attn_job(const vsim_model *m, const DevTables &tab, uint8_t *oq_qs, float *oq_d, float *oxd, int nsplit,
-                        float *kc, float *vc, const int *npast) {
+// the attention output leaves quantized in the row(s) o, every head over nsplit workgroups.  The
+// cache and the position come with attn_job: the layer's and the device position of the single-token
+// step; null for a rows batch, whose rows each have their own (AttnRows).
+AttnDesc decode_attn_desc(const vsim_model *m, const DevTables &tab, const ActRow &o, int nsplit) {
   const GraphDesc &G = m->gd;
   const int E = m->hp.n_embd, H = m->hp.n_head;
-  AttnJob A{};
-  A.q = m->Qb;
-  A.k = m->Kb;
-  A.v = m->Vb;
-  A.kc = kc;
-  A.vc = vc;
-  A.npast = npast;
-  A.cs = m->rope_cs;
-  A.etab = tab.exp_f16;
-  A.d = E / H;
-  A.H = H;
-  A.n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot;
-  A.style = G.rotary == ROT_GPTJ ? 1 : 0;
-  A.n_ctx = m->n_ctx;
-  A.nsplit = nsplit;
-  A.scale = m->attn_scale != 0.0f ? m->attn_scale : (float)(1.0f / std::sqrt((double)(float(E) / H)));
-  A.kqv_nth = m->kqv_nth;
-  A.alibi = G.alibi ? m->alibi : nullptr;
-  A.oq_qs = oq_qs;
-  A.oq_d = oq_d;
-  A.oxd = oxd;
-  A.out = nullptr;
-  return A;
+  return AttnDesc{.d = E / H, .H = H, .n_rot = G.rotary == ROT_NONE ? 0 : m->hp.n_rot,
+                  .style = G.rotary == ROT_GPTJ ? 1 : 0, .n_ctx = m->n_ctx, .nsplit = nsplit, .kqv_nth = m->kqv_nth,
+                  .scale = m->attn_scale != 0.0f ? m->attn_scale : default_attn_scale(E, H),
+                  .alibi = G.alibi ? m->alibi : nullptr, .q = m->Qb, .k = m->Kb, .v = m->Vb, .cs = m->rope_cs,
+                  .etab = tab.exp_f16, .o = o};
 }
 
 // One product of a Q4_0 weight with the batch's activation rows (PromptBatch::mm).  Every operand
@@ -846,15 +808,14 @@ int run_layer(PromptBatch &B, int il) {
     RC(B.mm(k));
   }
   RC(B.mm(v));
-  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
+  const float scale = default_attn_scale(E, H);
   if (rows) {
     // batched decode step: RoPE, the cache write, KQ, softmax, KQV and the out-projection's
     // activation quantize of every row in one launch, each row on its own cache at its own
     // position (attn.hpp, the single-token step's head); Q4 rows in launch_q4_quantize's layout
     DevTables tab;
     RC(tables_get(&tab));
-    AttnJob A = decode_attn_job(m, tab, m->xq2, (float *)(m->xq2 + (size_t)N * (E / QK) * 16), m->xd2, 1,
-                                nullptr, nullptr, nullptr);
+    AttnJob A = attn_job(decode_attn_desc(m, tab, ActRow{q4_rows(m->xq2, E, N), m->xd2}, 1), nullptr, nullptr, nullptr);
     if (w4a16) A.out = m->attn_in;  // the out-projection's operand is made from the f32 row
     const AttnRows R{D.rows->kc, D.rows->vc, loff, D.rows->npast};
     LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
@@ -957,12 +918,12 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
   DevTables tab;
   RC(tables_get(&tab));
   uint8_t *q1 = m->xq1, *q3 = m->xq3;
-  float *d1 = q4_scales(q1, E), *d2 = q4_scales(m->xq2, E), *d3 = q4_scales(q3, F);
+  float *d1 = q4_rows(q1, E).d, *d2 = q4_rows(m->xq2, E).d, *d3 = q4_rows(q3, F).d;
   if (m->first) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
   }
-  const float scale = (float)(1.0f / std::sqrt((double)(float(E) / H)));
+  const float scale = default_attn_scale(E, H);
   const int nchunk = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
   const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
   float *R[2] = {m->inpL, m->inpL2};
@@ -1017,7 +978,7 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     T.part = m->fast_part;
     T.hcnt = m->tail_done;
     T.oq_qs = m->xqa;
-    T.oq_d = q4_scales(m->xqa, E);
+    T.oq_d = q4_rows(m->xqa, E).d;
     // attention merge + out-projection + residual join into the other buffer
     FastOproj O{};
     O.w = w4_view(L.wo, E, E);
@@ -1069,17 +1030,201 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
 //   4. k_ln_quant: attn + bias + x joined, post-attention LayerNorm (BLOOM keeps the joined
 //      row as the residual, inpFF; GPT-NeoX's serial graph adds the MLP to the old one)
 //   5. GEMV fc_in (+ bias, GELU, requantize)       6. GEMV fc_out
+// What one enqueue of that step carries from launch to launch, and its recurring launches (their
+// jobs from decode_jobs.hpp).
+struct DecodeStep {
+  vsim_model *m;
+  int &nk;
+  const DevTables tab;
+  hipStream_t s;
+  const int E, F;
+  // the Q4 rows of the step: norm 1's, norm 2's, fc_in's GELU output, the attention output
+  const ActRow x1, x2, x3, xa;
+  // The residual join of layer l (inpL += attn + ff, vsim.cpp:694-695) runs inside layer
+  // l+1's LayerNorm kernel (or the final norm); the joined row goes to the other of the two
+  // residual buffers, so both norm workgroups of GPT-NeoX can read the old one.
+  float *R[2];
+  int cur = 0;
+  LnJoin pend;           // the join the last layer left to the next norm (jout null: none)
+  bool ln_done = false;  // the last layer's tail ran the next norm(s) (TailLn)
+  bool tail, lnt_ok;
+  int nsplit = 1;
+  // algorithmic bytes of the profiled launches (SURVEY.md §8(d)): KV rows read (P + 1) and
+  // written by the attention, rows of E floats read / written by the LayerNorm step
+  const double kv_bytes;
+
+  DecodeStep(vsim_model *m_, int &nk_, const DevTables &tab_)
+      : m(m_), nk(nk_), tab(tab_), s(m_->stream), E(m_->hp.n_embd), F(4 * E),
+        x1{q4_rows(m->xq1, E), m->xd1}, x2{q4_rows(m->xq2, E), m->xd2}, x3{q4_rows(m->xq3, F), m->xd3},
+        xa{q4_rows(m->xqa, E), m->xda}, R{m->inpL, m->inpL2},
+        kv_bytes(2.0 * ((double)m->prof_npast + 1) * E * sizeof(float)) {
+    const int d = E / m->hp.n_head;
+    const bool serial = m->gd.residual != RES_PARALLEL;
+    // the attention heads fuse into k_layer_tail while their LDS (scores over n_ctx) fits it
+    tail = m->mode == VSIM_MODE_EXACT && (size_t)attn_lds_floats(d, m->n_ctx) * sizeof(float) <= 75264;
+    // the next layer's LayerNorm inside the tail (TailLn; parallel-residual graphs: the tail is
+    // where both branches of the layer end)
+    lnt_ok = tail && !serial && m->l1 <= 255 && tail_ln_ok(E);
+    // each head over two workgroups (its KQV columns halved; the scores computed by both) in the
+    // parallel-residual fused tail, where it was measured: r05, 248-token GPT-J lines 608.9 / 612.5
+    // vs 606.9 / 610.8 tok/s unsplit, 602.6 / 601.3 at four (profiles/r05_tail_variants_ab.txt).
+    // The largest split <= ATT_SPLIT whose column parts are whole 32-blocks; the serial graphs'
+    // heads and the standalone k_attn_decode stay one workgroup per head.  (A/B builds:
+    // tools/build_variant.sh NAME model.cpp 's/ATT_SPLIT = 2/ATT_SPLIT = 1/'.)
+    constexpr int ATT_SPLIT = 2;
+    for (int sp = tail && !serial ? ATT_SPLIT : 1; sp > 1; --sp)
+      if (d % sp == 0 && (d / sp) % QK == 0) {
+        nsplit = sp;
+        break;
+      }
+  }
+
+  // reads: the row (+ the four join vectors), each norm's affine; writes: the joined row, each
+  // norm's factors xd (E floats) and Q4 row (0.625 B per value)
+  double ln_bytes(int nnorm, bool join) const {
+    return 4.0 * E * (1 + (join ? 5 : 0) + 3 * nnorm) + 0.625 * E * nnorm;
+  }
+  const LnJoin *pending() const { return pend.jout ? &pend : nullptr; }
+  // layer l ends with its branches unjoined: a (+ ab) and m->ff (+ fb) join x into the other buffer
+  void leave_join(const float *a, const float *ab, const float *fb) { pend = LnJoin{a, ab, m->ff, fb, R[cur ^ 1]}; }
+
+  // k_ln_quant: (join +) one or two norms of the residual row, quantized; a join that stores moves
+  // the residual to the other buffer.  first: the step's first norm advances the epoch (the tails' tags)
+  int ln_quant(const NormRow &n1, const NormRow *n2, const LnJoin *join, bool first) {
+    const LnQuantPair P = ln_quant_jobs(R[cur], n1, n2, join, tail && first ? m->tw.ep : nullptr);
+    LAUNCH(m, nk, launch_ln_quant(P.j1, P.second(), E, s), "k_ln_quant", ln_bytes(n2 ? 2 : 1, join != nullptr));
+    if (join && join->jout) cur ^= 1;
+    return VSIM_OK;
+  }
+  // (exact_kernel: the exact kernel's name as the profile has always had it for this product,
+  // where it does not ask gemv_chain_solo)
+  int gemv(const GemvBatch &Bt, const char *what, double bytes, const char *exact_kernel = nullptr) {
+    if (!exact_kernel) exact_kernel = gemv_chain_solo(Bt) ? "k_gemv_solo" : "k_gemv_chain32";
+    LAUNCH(m, nk, launch_gemv_epi(Bt, m->mode, s),
+           std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : exact_kernel) + " (" + what + ")", bytes);
+    return VSIM_OK;
+  }
+  // attention for the new token (attn.hpp) on layer il's cache: inside k_layer_tail beside the
+  // products f and o (and the next norms N), or alone
+  AttnJob attn(int il) const {
+    const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
+    return attn_job(decode_attn_desc(m, tab, xa, nsplit), m->kcache + loff, m->vcache + loff, m->npast_dev);
+  }
+  int layer_tail(const GemvBatch &f, const GemvBatch &o, int il, const TailLn *N, const char *name, double w_bytes) {
+    LAUNCH(m, nk, launch_layer_tail(f, o, attn(il), TailSync{m->tw.hflag, m->tw.ep, il}, m->n_ctx, s, N), name,
+           w_bytes + kv_bytes + (N ? ln_bytes(N->w2 ? 2 : 1, true) : 0.0));
+    return VSIM_OK;
+  }
+  int attn_decode(int il) {
+    LAUNCH(m, nk, launch_attn_decode(attn(il), m->n_ctx, s), "k_attn_decode", kv_bytes);
+    return VSIM_OK;
+  }
+
+  // One serial-residual layer (steps 1-6 above)
+  int layer_serial(int il) {
+    const LayerW &L = m->layers[il - m->l0];
+    // 1. (join +) input LayerNorm + quantize
+    RC(ln_quant(NormRow{L.ln1_w, L.ln1_b, x1}, nullptr, pending(), il == m->l0));
+    // 2. Q, K, V (+ bias; BLOOM: the fused query_key_value's row blocks)
+    const GemvBatch B = gemv_batch({gemv_job(L.wq, E, E, x1, L.bq, m->Qb), gemv_job(L.wk, E, E, x1, L.bk, m->Kb),
+                                    gemv_job(L.wv, E, E, x1, L.bv, m->Vb)});
+    RC(gemv(B, "Q, K, V", 3 * w4_algo_bytes(B.j[0].w)));
+    // 3. heads + out-projection (its bias joins in step 4)
+    const GemvBatch Bo = gemv_batch({gemv_job(L.wo, E, E, xa, nullptr, m->attn)});
+    if (tail) {
+      RC(layer_tail(GemvBatch{}, Bo, il, nullptr, "k_layer_tail (attention + out-proj)", w4_algo_bytes(Bo.j[0].w)));
+    } else {
+      RC(attn_decode(il));
+      RC(gemv(Bo, "out-proj", w4_algo_bytes(Bo.j[0].w)));
+    }
+    // 4. inpFF = (attn + b_o) + x, post-attention LayerNorm + quantize
+    const LnJoin j4{m->attn, L.bo, nullptr, nullptr, m->gd.residual == RES_SERIAL_JOINED ? R[cur ^ 1] : nullptr};
+    RC(ln_quant(NormRow{L.ln2_w, L.ln2_b, x2}, nullptr, &j4, false));
+    // 5. fc_in (+ bias, GELU, requantize)   6. fc_out (its bias joins in the next step 1)
+    GemvBatch Bi = gemv_batch({gemv_job(L.wfc, F, E, x2, L.bfc, nullptr)});
+    gelu_quant_into(Bi.j[0], tab.gelu_f16, x3);
+    RC(gemv(Bi, "fc_in", w4_algo_bytes(Bi.j[0].w)));
+    const GemvBatch Bf = gemv_batch({gemv_job(L.wproj, E, F, x3, nullptr, m->ff)});
+    RC(gemv(Bf, "fc_out", w4_algo_bytes(Bf.j[0].w)));
+    leave_join(nullptr, nullptr, L.bproj);
+    return VSIM_OK;
+  }
+
+  // One parallel-residual layer (steps 1-3 above)
+  int layer_parallel(int il) {
+    const GraphDesc &G = m->gd;
+    const LayerW &L = m->layers[il - m->l0];
+    // 1. (join +) LayerNorm(s) + quantize, unless the previous layer's tail ran them (TailLn)
+    if (!ln_done) {
+      const NormRow n1{L.ln1_w, L.ln1_b, x1}, n2{L.ln2_w, L.ln2_b, x2};
+      RC(ln_quant(n1, G.two_norms ? &n2 : nullptr, pending(), il == m->l0));
+    }
+    ln_done = false;
+    // 2. {fc_in (+bias, GELU, requantize), Q, K, V}
+    GemvBatch B = gemv_batch({gemv_job(L.wfc, F, E, G.two_norms ? x2 : x1, L.bfc, nullptr),
+                              gemv_job(L.wq, E, E, x1, G.qkvo_bias ? L.bq : nullptr, m->Qb),
+                              gemv_job(L.wk, E, E, x1, G.qkvo_bias ? L.bk : nullptr, m->Kb),
+                              gemv_job(L.wv, E, E, x1, G.qkvo_bias ? L.bv : nullptr, m->Vb)});
+    gelu_quant_into(B.j[0], tab.gelu_f16, x3);
+    RC(gemv(B, "fc_in, Q, K, V", w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w), "k_gemv_solo"));
+    // 3. attention for the new token (attn.hpp), fc_out and the out-projection
+    GemvBatch Bf = gemv_batch({gemv_job(L.wproj, E, F, x3, nullptr, m->ff)});
+    const GemvBatch Bo = gemv_batch({gemv_job(L.wo, E, E, xa, nullptr, m->attn)});
+    const double w_bytes = w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w);
+    const float *ab = G.qkvo_bias ? L.bo : nullptr;
+    // the next LayerNorm inside this tail: every layer but a non-last stage's last one
+    if (lnt_ok && (il + 1 < m->l1 || m->last)) {
+      NormRow n1{m->lnf_w, m->lnf_b, x1}, n2;  // the final norm, for the lm_head
+      const bool next = il + 1 < m->l1;          // or the next layer's input norm(s)
+      if (next) {
+        const LayerW &Ln = m->layers[il + 1 - m->l0];
+        n1 = NormRow{Ln.ln1_w, Ln.ln1_b, x1};
+        n2 = NormRow{Ln.ln2_w, Ln.ln2_b, x2};
+      }
+      const TailLn N = tail_ln_job(R[cur], R[cur ^ 1], ab, L.bproj, n1, next && G.two_norms ? &n2 : nullptr, m->tw,
+                                   dev_stats(), il);
+      RC(layer_tail(Bf, Bo, il, &N, "k_layer_tail (fc_out + attention + out-proj + join + LayerNorm)", w_bytes));
+      cur ^= 1;
+      ln_done = true;
+      pend = LnJoin{};
+      return VSIM_OK;
+    }
+    if (tail) {
+      RC(layer_tail(Bf, Bo, il, nullptr, "k_layer_tail (fc_out + attention + out-proj)", w_bytes));
+    } else {
+      RC(attn_decode(il));
+      Bf.j[Bf.nj++] = Bo.j[0];
+      RC(gemv(Bf, "fc_out, out-proj", w_bytes, "k_gemv_chain32"));
+    }
+    leave_join(m->attn, ab, L.bproj);
+    return VSIM_OK;
+  }
+
+  // The stage's end: the final norm (unless the last tail ran it) and the lm_head, or on a non-last
+  // stage the join the last layer left
+  int head() {
+    if (m->last) {
+      if (!ln_done) RC(ln_quant(NormRow{m->lnf_w, m->lnf_b, x1}, nullptr, pending(), false));
+      const GemvBatch B = gemv_batch(
+          {gemv_job(m->lmh, m->hp.n_vocab, E, x1, m->gd.lmh_bias ? m->lmh_b : nullptr, m->logits)});
+      RC(gemv(B, "lm_head", w4_algo_bytes(B.j[0].w), "k_gemv_solo"));
+    } else if (const LnJoin *j = pending()) {
+      RC(launch_residual_join(R[cur], j->ja, j->jab, j->jf, j->jfb, j->jout, E, s));
+      ++nk;
+      cur ^= 1;
+    }
+    m->resid_final = R[cur];
+    return VSIM_OK;
+  }
+};
+
 int enqueue_decode(vsim_model *m, int &nk) {
   if (m->mode == VSIM_MODE_FAST && fast_decode_ok(m)) return enqueue_decode_fast(m, nk);
-  const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H, F = 4 * E, V = m->hp.n_vocab;
-  const GraphDesc &G = m->gd;
-  const bool serial = G.residual != RES_PARALLEL;
+  const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
-  uint8_t *q1 = m->xq1, *q2 = m->xq2, *q3 = m->xq3, *qa = m->xqa;
-  float *d1 = q4_scales(q1, E), *d2 = q4_scales(q2, E), *d3 = q4_scales(q3, F), *da = q4_scales(qa, E);
-  if (m->first && G.emb_norm) {  // word embeddings + word_embeddings_layernorm
+  if (m->first && m->gd.emb_norm) {  // word embeddings + word_embeddings_layernorm
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->cur1, s));
     RC(launch_norm(m->cur1, m->inpL, E, 1, m->emb_w, m->emb_b, s));
     nk += 2;
@@ -1087,232 +1232,10 @@ int enqueue_decode(vsim_model *m, int &nk) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
   }
-  // algorithmic bytes of the profiled launches (SURVEY.md §8(d)): KV rows read (P + 1) and
-  // written by the attention, rows of E floats read / written by the LayerNorm step
-  const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
-  // reads: the row (+ the four join vectors), each norm's affine; writes: the joined row, each
-  // norm's factors xd (E floats) and Q4 row (0.625 B per value)
-  auto ln_bytes = [&](int nnorm, bool join) {
-    return 4.0 * E * (1 + (join ? 5 : 0) + 3 * nnorm) + 0.625 * E * nnorm;
-  };
-  // The residual join of layer l (inpL += attn + ff, vsim.cpp:694-695) runs inside layer
-  // l+1's LayerNorm kernel (or the final norm); the joined row goes to the other of the two
-  // residual buffers, so both norm workgroups of GPT-NeoX can read the old one.
-  float *R[2] = {m->inpL, m->inpL2};
-  int cur = 0;
-  bool pending = false, ln_done = false;
-  const float *pend_a = nullptr, *pend_ab = nullptr, *pend_fb = nullptr;
-  auto join_into = [&](LnQuantJob &j, bool write) {
-    j.ja = pend_a;
-    j.jab = pend_ab;
-    j.jf = m->ff;
-    j.jfb = pend_fb;
-    j.jout = write ? R[cur ^ 1] : nullptr;
-  };
-  auto job = [&](GemvBatch &Bt, int i, void *W, int M, int K, const float *xd, const uint8_t *xq, const float *xdd,
-                 const float *bias, float *y) {
-    GemvJob &J = Bt.j[i];
-    J.w = w4_view(W, M, K);
-    J.xd = xd;
-    J.xqs = xq;
-    J.xdd = xdd;
-    J.bias = bias;
-    J.y = y;
-    J.epi = EPI_STORE;
-  };
-  // the attention heads fuse into k_layer_tail while their LDS (scores over n_ctx) fits it
-  const bool tail = m->mode == VSIM_MODE_EXACT && (size_t)attn_lds_floats(d, m->n_ctx) * sizeof(float) <= 75264;
-  // the next layer's LayerNorm inside the tail (TailLn; parallel-residual graphs: the tail is
-  // where both branches of the layer end)
-  const bool lnt_ok = tail && !serial && m->l1 <= 255 && tail_ln_ok(E);
-  // each head over two workgroups (its KQV columns halved; the scores computed by both) in the
-  // parallel-residual fused tail, where it was measured: r05, 248-token GPT-J lines 608.9 / 612.5
-  // vs 606.9 / 610.8 tok/s unsplit, 602.6 / 601.3 at four (profiles/r05_tail_variants_ab.txt).
-  // The largest split <= ATT_SPLIT whose column parts are whole 32-blocks; the serial graphs'
-  // heads and the standalone k_attn_decode stay one workgroup per head.  (A/B builds:
-  // tools/build_variant.sh NAME model.cpp 's/ATT_SPLIT = 2/ATT_SPLIT = 1/'.)
-  constexpr int ATT_SPLIT = 2;
-  int nsplit = 1;
-  for (int sp = tail && !serial ? ATT_SPLIT : 1; sp > 1; --sp)
-    if (d % sp == 0 && (d / sp) % QK == 0) {
-      nsplit = sp;
-      break;
-    }
-  auto attn_job = [&](size_t loff) {
-    return decode_attn_job(m, tab, qa, da, m->xda, nsplit, m->kcache + loff, m->vcache + loff, m->npast_dev);
-  };
-  // (exact_kernel: the exact kernel's name as the profile has always had it for this product,
-  // where it does not ask gemv_chain_solo)
-  auto gemv = [&](const GemvBatch &Bt, const char *what, double bytes, const char *exact_kernel = nullptr) -> int {
-    if (!exact_kernel) exact_kernel = gemv_chain_solo(Bt) ? "k_gemv_solo" : "k_gemv_chain32";
-    LAUNCH(m, nk, launch_gemv_epi(Bt, m->mode, s),
-           std::string(m->mode != VSIM_MODE_EXACT ? "k_gemv_fast_epi" : exact_kernel) + " (" + what + ")", bytes);
-    return VSIM_OK;
-  };
-  for (int il = m->l0; il < m->l1; ++il) {
-    const LayerW &L = m->layers[il - m->l0];
-    const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
-    if (serial) {
-      // 1. (join +) input LayerNorm + quantize
-      LnQuantJob j1{R[cur], L.ln1_w, L.ln1_b, q1, d1, m->xd1};
-      if (pending) join_into(j1, true);
-      if (tail && il == m->l0) j1.ep = m->lnt_ep;  // the step's epoch (the tail's flags)
-      LAUNCH(m, nk, launch_ln_quant(j1, nullptr, E, s), "k_ln_quant", ln_bytes(1, pending));
-      if (pending) cur ^= 1;
-      // 2. Q, K, V (+ bias; BLOOM: the fused query_key_value's row blocks)
-      GemvBatch B{};
-      B.nj = 3;
-      job(B, 0, L.wq, E, E, m->xd1, q1, d1, L.bq, m->Qb);
-      job(B, 1, L.wk, E, E, m->xd1, q1, d1, L.bk, m->Kb);
-      job(B, 2, L.wv, E, E, m->xd1, q1, d1, L.bv, m->Vb);
-      RC(gemv(B, "Q, K, V", 3 * w4_algo_bytes(B.j[0].w)));
-      // 3. heads + out-projection (its bias joins in step 4)
-      const AttnJob A = attn_job(loff);
-      GemvBatch Bo{};
-      Bo.nj = 1;
-      job(Bo, 0, L.wo, E, E, m->xda, qa, da, nullptr, m->attn);
-      if (tail) {
-        GemvBatch none{};
-        LAUNCH(m, nk, launch_layer_tail(none, Bo, A, TailSync{m->tail_hflag, m->lnt_ep, il}, m->n_ctx, s),
-               "k_layer_tail (attention + out-proj)", w4_algo_bytes(Bo.j[0].w) + kv_bytes);
-      } else {
-        LAUNCH(m, nk, launch_attn_decode(A, m->n_ctx, s), "k_attn_decode", kv_bytes);
-        RC(gemv(Bo, "out-proj", w4_algo_bytes(Bo.j[0].w)));
-      }
-      // 4. inpFF = (attn + b_o) + x, post-attention LayerNorm + quantize
-      LnQuantJob j2{R[cur], L.ln2_w, L.ln2_b, q2, d2, m->xd2};
-      j2.ja = m->attn;
-      j2.jab = L.bo;
-      j2.jout = G.residual == RES_SERIAL_JOINED ? R[cur ^ 1] : nullptr;
-      LAUNCH(m, nk, launch_ln_quant(j2, nullptr, E, s), "k_ln_quant", ln_bytes(1, true));
-      if (G.residual == RES_SERIAL_JOINED) cur ^= 1;
-      // 5. fc_in (+ bias, GELU, requantize)   6. fc_out (its bias joins in the next step 1)
-      GemvBatch Bi{};
-      Bi.nj = 1;
-      job(Bi, 0, L.wfc, F, E, m->xd2, q2, d2, L.bfc, nullptr);
-      Bi.j[0].epi = EPI_GELU_Q;
-      Bi.j[0].gelu_tab = tab.gelu_f16;
-      Bi.j[0].oq_qs = q3;
-      Bi.j[0].oq_d = d3;
-      Bi.j[0].oxd = m->xd3;
-      RC(gemv(Bi, "fc_in", w4_algo_bytes(Bi.j[0].w)));
-      GemvBatch Bf{};
-      Bf.nj = 1;
-      job(Bf, 0, L.wproj, E, F, m->xd3, q3, d3, nullptr, m->ff);
-      RC(gemv(Bf, "fc_out", w4_algo_bytes(Bf.j[0].w)));
-      pending = true;
-      pend_a = nullptr;
-      pend_ab = nullptr;
-      pend_fb = L.bproj;
-      continue;
-    }
-    // 1. (join +) LayerNorm(s) + quantize, unless the previous layer's tail ran them (TailLn)
-    const TailSync sy{m->tail_hflag, m->lnt_ep, il};  // the heads' flags of this layer's tail
-    if (!ln_done) {
-      LnQuantJob j1{R[cur], L.ln1_w, L.ln1_b, q1, d1, m->xd1};
-      LnQuantJob j2{R[cur], L.ln2_w, L.ln2_b, q2, d2, m->xd2};
-      if (pending) {
-        join_into(j1, true);
-        join_into(j2, false);
-      }
-      if (tail && il == m->l0) j1.ep = m->lnt_ep;  // the step's first norm advances the epoch
-      LAUNCH(m, nk, launch_ln_quant(j1, G.two_norms ? &j2 : nullptr, E, s), "k_ln_quant",
-             ln_bytes(G.two_norms ? 2 : 1, pending));
-      if (pending) cur ^= 1;
-    }
-    ln_done = false;
-    // 2. {fc_in (+bias, GELU, requantize), Q, K, V}
-    GemvBatch B{};
-    B.nj = 4;
-    job(B, 0, L.wfc, F, E, G.two_norms ? m->xd2 : m->xd1, G.two_norms ? q2 : q1, G.two_norms ? d2 : d1, L.bfc, nullptr);
-    B.j[0].epi = EPI_GELU_Q;
-    B.j[0].gelu_tab = tab.gelu_f16;
-    B.j[0].oq_qs = q3;
-    B.j[0].oq_d = d3;
-    B.j[0].oxd = m->xd3;
-    job(B, 1, L.wq, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bq : nullptr, m->Qb);
-    job(B, 2, L.wk, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bk : nullptr, m->Kb);
-    job(B, 3, L.wv, E, E, m->xd1, q1, d1, G.qkvo_bias ? L.bv : nullptr, m->Vb);
-    RC(gemv(B, "fc_in, Q, K, V", w4_algo_bytes(B.j[0].w) + 3 * w4_algo_bytes(B.j[1].w), "k_gemv_solo"));
-    // 3. attention for the new token (attn.hpp), fc_out and the out-projection
-    const AttnJob A = attn_job(loff);
-    GemvBatch Bf{}, Bo{};
-    Bf.nj = 1;
-    job(Bf, 0, L.wproj, E, F, m->xd3, q3, d3, nullptr, m->ff);
-    Bo.nj = 1;
-    job(Bo, 0, L.wo, E, E, m->xda, qa, da, nullptr, m->attn);
-    // the next LayerNorm inside this tail: every layer but a non-last stage's last one
-    const bool lnt = tail && lnt_ok && (il + 1 < m->l1 || m->last);
-    if (lnt) {
-      TailLn N{};
-      N.x = R[cur];
-      N.ab = G.qkvo_bias ? L.bo : nullptr;
-      N.fb = L.bproj;
-      N.jout = R[cur ^ 1];
-      if (il + 1 < m->l1) {  // the next layer's input norm(s)
-        const LayerW &Ln = m->layers[il + 1 - m->l0];
-        N.w1 = Ln.ln1_w;
-        N.b1 = Ln.ln1_b;
-        if (G.two_norms) {
-          N.w2 = Ln.ln2_w;
-          N.b2 = Ln.ln2_b;
-          N.q2 = q2;
-          N.d2 = d2;
-          N.xd2 = m->xd2;
-        }
-      } else {  // the final norm, for the lm_head
-        N.w1 = m->lnf_w;
-        N.b1 = m->lnf_b;
-      }
-      N.q1 = q1;
-      N.d1 = d1;
-      N.xd1 = m->xd1;
-      N.og = m->lnt_og;
-      N.jg = m->lnt_jg;
-      N.rec = m->lnt_rec;
-      N.ep = m->lnt_ep;
-      N.stats = dev_stats();
-      N.il = il;
-      LAUNCH(m, nk, launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s, &N),
-             "k_layer_tail (fc_out + attention + out-proj + join + LayerNorm)",
-             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes + ln_bytes(N.w2 ? 2 : 1, true));
-      cur ^= 1;
-      ln_done = true;
-      pending = false;
-      continue;
-    }
-    if (tail) {
-      LAUNCH(m, nk, launch_layer_tail(Bf, Bo, A, sy, m->n_ctx, s), "k_layer_tail (fc_out + attention + out-proj)",
-             w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bo.j[0].w) + kv_bytes);
-    } else {
-      LAUNCH(m, nk, launch_attn_decode(A, m->n_ctx, s), "k_attn_decode", kv_bytes);
-      Bf.j[1] = Bo.j[0];
-      Bf.nj = 2;
-      RC(gemv(Bf, "fc_out, out-proj", w4_algo_bytes(Bf.j[0].w) + w4_algo_bytes(Bf.j[1].w), "k_gemv_chain32"));
-    }
-    pending = true;
-    pend_a = m->attn;
-    pend_ab = G.qkvo_bias ? L.bo : nullptr;
-    pend_fb = L.bproj;
-  }
-  if (m->last) {
-    if (!ln_done) {
-      LnQuantJob jf{R[cur], m->lnf_w, m->lnf_b, q1, d1, m->xd1};
-      if (pending) join_into(jf, true);
-      LAUNCH(m, nk, launch_ln_quant(jf, nullptr, E, s), "k_ln_quant", ln_bytes(1, pending));
-      if (pending) cur ^= 1;
-    }
-    GemvBatch B{};
-    B.nj = 1;
-    job(B, 0, m->lmh, V, E, m->xd1, q1, d1, G.lmh_bias ? m->lmh_b : nullptr, m->logits);
-    RC(gemv(B, "lm_head", w4_algo_bytes(B.j[0].w), "k_gemv_solo"));
-  } else if (pending) {
-    RC(launch_residual_join(R[cur], pend_a, pend_ab, m->ff, pend_fb, R[cur ^ 1], E, s));
-    ++nk;
-    cur ^= 1;
-  }
-  m->resid_final = R[cur];
-  return VSIM_OK;
+  DecodeStep S(m, nk, tab);
+  for (int il = m->l0; il < m->l1; ++il)
+    RC(m->gd.residual != RES_PARALLEL ? S.layer_serial(il) : S.layer_parallel(il));
+  return S.head();
 }
 
 thread_local std::string t_err;
