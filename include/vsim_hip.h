@@ -250,6 +250,67 @@ int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n
 int vsim_op_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, void *stream);
 int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, const int32_t *e, int n,
                                const float *bias, float *y, void *stream);
+/* ---- weight-only mode: the kernels of the single-token step (w4a16_decode.hip).  Each is, bit for
+ * bit, a composition of entries above on the same row; none has a tolerance of its own.
+ *
+ * vsim_op_w4a16_ln (k_w4a16_ln): for one row x[n],
+ *   (x16_1, e1) = vsim_op_w4a16_rows(vsim_op_norm(x, w1, b1)), and, when the second norm is given,
+ *   (x16_2, e2) = vsim_op_w4a16_rows(vsim_op_norm(x, w2, b2)) as a second workgroup of the launch.
+ * The f32 norm row is not written anywhere.  The maximum behind e is taken over the affine's outputs
+ * w y + b.  vsim_norm_fallbacks counts what vsim_op_norm would count for the same rows (each norm
+ * counts on its own).  VSIM_EINVAL: n not a positive multiple of 32 or beyond 16,384 (the LDS row,
+ * vsim_op_norm's limit); a NULL x, w1, b1, x16_1 or e1; a second norm with some but not all of w2, b2,
+ * x16_2, e2; x, an affine vector or an operand not 16-byte aligned. */
+typedef struct {
+  const float *x; /* [n] */
+  int32_t n;
+  const float *w1, *b1;
+  void *x16_1; /* [n] halves */
+  int32_t *e1;
+  const float *w2, *b2; /* all four NULL: one norm */
+  void *x16_2;
+  int32_t *e2;
+} vsim_w4a16_ln_args;
+int vsim_op_w4a16_ln(const vsim_w4a16_ln_args *a, void *stream);
+/* vsim_op_w4a16_gelu (k_w4a16_gelu): for one row x[K],
+ *   g[i] = fp16->fp32(table_gelu_f16[fp32->fp16(x[i] + bias[i])])   (vsim_op_gelu; bias NULL: no add),
+ *   (x16, e) = vsim_op_w4a16_rows(g), and g itself to g_or_null when given.
+ * The maximum behind e is taken over g, not over x + bias; a row whose g is all zero gets e = 0; an
+ * x + bias beyond fp16 range reads the table's entry for +-inf, which is not finite, so such a row
+ * is VSIM_W4A16_NONFINITE although its input is finite.  K of any size (rows up to 24,576 keep g in registers, longer rows make it
+ * twice; same bits).  VSIM_EINVAL: K not a positive multiple of 32; a NULL x, x16 or e; x, bias, x16
+ * or g not 16-byte aligned. */
+int vsim_op_w4a16_gelu(const float *x, const float *bias, int K, void *x16, int32_t *e, float *g_or_null,
+                       void *stream);
+/* vsim_op_w4a16_gemv (k_gemv_w4a16): nj = 1..4 products in one launch, each of a W4T32 weight
+ * w [M][K] with a single-row operand (x16, e) of its own.  Per job, with
+ *   v = vsim_op_q4_gemm_w4a16_rows(w, M, K, x16, e, n = 1, bias)      (bit for bit, NaN rule included),
+ *   y = v                      (res NULL),
+ *   y = v + res                (res alone),
+ *   y = res + (res_a + v)      (res and res_a; both orders are the residual joins' of the model).
+ * A thread reads only the res / res_a elements it writes, so y may be res.  A job's outputs do not
+ * depend on the jobs beside it.  Nothing past M is written or read of bias, res, res_a and y, nothing
+ * past K of x16, nothing behind the weight.  VSIM_EINVAL: nj outside 1..4; a job with K not a positive
+ * multiple of 32, M <= 0, or a NULL w, x16, e or y; res_a without res; w or x16 not 16-byte aligned.
+ * All three are enqueued on stream and not synchronized. */
+typedef struct {
+  const void *w; /* W4T32 [M][K] */
+  int32_t M, K;
+  const void *x16; /* [K] halves */
+  const int32_t *e;
+  const float *bias, *res, *res_a; /* [M] each, or NULL */
+  float *y;                        /* [M] */
+} vsim_w4a16_gemv_job;
+typedef struct {
+  vsim_w4a16_gemv_job j[4];
+  int32_t nj;
+} vsim_w4a16_gemv_args;
+int vsim_op_w4a16_gemv(const vsim_w4a16_gemv_args *a, void *stream);
+/* Process-wide switch of weight-only mode's single-token step (vsim_model_set_mode): 1 (default) the
+ * fused step, 0 the general path for every single-token call, as before the step existed.  Same bits
+ * either way.  Models drop their captured step graphs when they next run after a change.  Returns
+ * the previous value. */
+int vsim_w4a16_set_step(int enable);
 /* Process-wide choice of how vsim_op_q4_gemm_fast_rows and the products of
  * vsim_model_decode_batch_fast run: 0: one k_gemv_fast launch per row (the weight streams once per
  * row); 1 (default): k_gemm_fast_rows from the smallest row count where it was measured faster by
@@ -779,11 +840,18 @@ int vsim_model_randomize(vsim_model *m, uint64_t seed, float std);
  *     whatever the head's chunk size;
  *   - row b of vsim_model_decode_batch_w4a16 is vsim_model_eval_seq's row for that sequence alone;
  *   - switching to another mode and back changes neither mode's bits.
- * All whole-model entry points work in the mode: vsim_model_eval, _eval_seq and _eval_score on the
- * general path (N = 1 included), _eval_argmax, _generate, _eval_sample and _generate_sampled as
- * uncaptured general-path steps on slot 0 with one host round trip per token (no hipGraph in this
- * mode yet).  The pipeline stage calls (vsim_model_stage_bind / _begin / _step) return VSIM_EINVAL
- * while the model is in this mode. */
+ * All whole-model entry points work in the mode.  vsim_model_eval_seq and _eval_score run the general
+ * path at every N, and so does vsim_model_eval at N > 1.  vsim_model_eval at N = 1, _eval_argmax,
+ * _generate, _eval_sample and _generate_sampled run the mode's single-token step on slot 0
+ * (w4a16_decode.hip: vsim_op_w4a16_ln, _gemv and _gelu around k_attn_decode_batch at one row; at most
+ * 7 launches per parallel-residual layer, 9 per serial one, 2 for the head), replayed as a hipGraph
+ * under vsim_model_set_graph like the other modes' steps, _generate without a host round trip per
+ * token.  The step's logits and cache rows are the general path's, bit for bit.  Shapes the step
+ * does not take run the general path as before (decided once per model): a head dim that is not a
+ * multiple of 32 or exceeds 256, n_embd beyond 16,384, or a context whose attention scores do not
+ * fit the attention kernel's LDS (2 d + n_ctx + 16,384 floats beyond 160 KB).  vsim_w4a16_set_step(0)
+ * puts every model back on the general path.  The pipeline stage calls (vsim_model_stage_bind /
+ * _begin / _step) return VSIM_EINVAL while the model is in this mode. */
 int vsim_model_set_mode(vsim_model *m, int mode);
 /* Allocates ahead what a prompt of up to n_tokens sets up on its first eval (the N-token
  * scratch, the fp16 key copies of the prompt attention, the GEMMs' stream-K workspace) and

@@ -187,6 +187,32 @@ int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, con
   }
   return launch_gemm_w4a16_rows(w4_view(w, M, K), x16, e, n, bias, y, (hipStream_t)stream);
 }
+int vsim_op_w4a16_ln(const vsim_w4a16_ln_args *a, void *stream) {
+  if (!a) { set_error("w4a16_ln: null argument"); return VSIM_EINVAL; }
+  DevTables tab;  // (the device's LayerNorm counters come with its tables)
+  RC(tables_get(&tab));
+  return launch_w4a16_ln(W4a16Ln{a->x, a->n, a->w1, a->b1, (_Float16 *)a->x16_1, a->e1, a->w2, a->b2,
+                                 (_Float16 *)a->x16_2, a->e2},
+                         (hipStream_t)stream);
+}
+int vsim_op_w4a16_gelu(const float *x, const float *bias, int K, void *x16, int32_t *e, float *g_or_null,
+                       void *stream) {
+  return launch_w4a16_gelu(x, bias, K, x16, e, g_or_null, (hipStream_t)stream);
+}
+int vsim_op_w4a16_gemv(const vsim_w4a16_gemv_args *a, void *stream) {
+  if (!a || a->nj < 1 || a->nj > 4) { set_error("w4a16_gemv: 1..4 jobs"); return VSIM_EINVAL; }
+  W4a16Gemv B{};
+  B.nj = a->nj;
+  for (int i = 0; i < a->nj; ++i) {
+    const vsim_w4a16_gemv_job &j = a->j[i];
+    if (!j.w || j.M <= 0 || j.K <= 0 || j.K % QK) {
+      set_error("w4a16_gemv: every job needs K a positive multiple of 32, M > 0, w, x16, e and y");
+      return VSIM_EINVAL;
+    }
+    B.j[i] = W4a16GemvJob{w4_view(j.w, j.M, j.K), (const _Float16 *)j.x16, j.e, j.bias, j.res, j.res_a, j.y};
+  }
+  return launch_w4a16_gemv(B, (hipStream_t)stream);
+}
 int vsim_batch_set_gemm(int enable) { return batch_set_gemm(enable); }
 int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {

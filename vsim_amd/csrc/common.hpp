@@ -327,6 +327,39 @@ int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias,
 int launch_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, hipStream_t s);
 int launch_gemm_w4a16_rows(const W4 &W, const void *x16, const int32_t *e, int n, const float *bias, float *y,
                            hipStream_t s);
+// Weight-only mode's single-token step (w4a16_decode.hip; vsim_op_w4a16_ln, _gelu, _gemv): each the
+// bits of the kernels above (and launch_norm, launch_gelu, launch_add_residual) on the same row.
+// LayerNorm of x[n] with (w1, b1) straight to the row operand (h1, e1), and optionally with (w2, b2)
+// to (h2, e2) as a second workgroup of the launch; the f32 norm row stays in LDS.  stats: dev_stats()
+struct W4a16Ln {
+  const float *x;
+  int n;
+  const float *w1, *b1;
+  _Float16 *h1;
+  int32_t *e1;
+  const float *w2, *b2;  // null: one norm
+  _Float16 *h2;
+  int32_t *e2;
+};
+int launch_w4a16_ln(const W4a16Ln &A, hipStream_t s);
+// g = gelu_table[f2h(x + bias)] of one row x[K] (bias may be null: no add), to the row operand
+// (x16, e) of g, and to g_out as f32 when that is given
+int launch_w4a16_gelu(const float *x, const float *bias, int K, void *x16, int32_t *e, float *g_out, hipStream_t s);
+// 1..4 products of a W4T32 weight with a single-row operand in one launch: workgroups take job 0's
+// groups of 16 weight rows, then job 1's, ...  v = k_gemm_w4a16_rows' value for the row; y = v,
+// or v + res (res alone), or res + (res_a + v) (k_add_residual's orders; y may be res)
+struct W4a16GemvJob {
+  W4 w;
+  const _Float16 *x16;
+  const int32_t *e;
+  const float *bias, *res, *res_a;
+  float *y;
+};
+struct W4a16Gemv {
+  W4a16GemvJob j[4];
+  int nj;
+};
+int launch_w4a16_gemv(const W4a16Gemv &B, hipStream_t s);
 int launch_act_repack(const void *aos, void *xq, int n, int k, hipStream_t s);
 int launch_act_unpack(const void *xq, void *aos, int n, int k, hipStream_t s);
 int launch_q4_dequant(const void *xq, int rows, int k, float *y, hipStream_t s);

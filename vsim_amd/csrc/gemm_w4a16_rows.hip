@@ -29,18 +29,11 @@
 //
 // Loads: in bounds without slack, as there: the last tile's padding rows exist (d = 0), the second
 // block of a trip is clamped to the last block, activation rows >= n are clamped to row n - 1.
-#include "kern.hpp"
-#include "../../include/vsim_hip.h"
+#include "w4a16.hpp"
 
 namespace vsim {
 
-constexpr int WA_RT = 16;     // weight rows per workgroup
-constexpr int WA_WAVES = 16;  // one per partial
-constexpr int WA_THREADS = 64 * WA_WAVES;
 constexpr int WA_OP_NT = 256;  // the operand kernel's threads
-
-typedef _Float16 wa_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 wa_half2 __attribute__((ext_vector_type(2)));
 
 // ------------------------------------------------------------------ the row operand
 __global__ void __launch_bounds__(WA_OP_NT)
@@ -76,7 +69,6 @@ __global__ void __launch_bounds__(WA_OP_NT)
 // and the conversion), four halves stored at a time.  The maximum does not depend on the order it is
 // taken in and the conversion is per element: the bits are k_w4a16_rows'.
 constexpr int WA_OPV_NT = 1024, WA_OPV_PER = 4, WA_OPV_MAXK = 4 * WA_OPV_NT * WA_OPV_PER;
-typedef _Float16 wa_half4 __attribute__((ext_vector_type(4)));
 
 __global__ void __launch_bounds__(WA_OPV_NT)
     k_w4a16_rows_v4(const float *__restrict__ x, int K, _Float16 *__restrict__ x16, int32_t *__restrict__ e_out) {
@@ -119,20 +111,6 @@ __global__ void __launch_bounds__(WA_OPV_NT)
 }
 
 // ------------------------------------------------------------------ the product
-// 8 nibbles of one word (element t at bits 4 t) as 8 halves q - 8: 0x6400 | q is the half 1024 + q
-__device__ __forceinline__ wa_half8 wa_unpack(uint32_t w) {
-  wa_half8 r;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t by = (w >> (8 * j)) & 0xFFu;
-    const uint32_t bits = 0x64006400u | (by & 0xFu) | ((by & 0xF0u) << 12);
-    const wa_half2 v = __builtin_bit_cast(wa_half2, bits) - wa_half2{(_Float16)1032.0f, (_Float16)1032.0f};
-    r[2 * j] = v[0];
-    r[2 * j + 1] = v[1];
-  }
-  return r;
-}
-
 template <int NJ>
 struct WaBlock {
   uint32_t wq;      // the lane's 4 bytes of its weight row's nibble run

@@ -137,6 +137,10 @@ struct vsim_model {
   int32_t *tok_host = nullptr;  // pinned
   float *logit_host = nullptr;  // pinned
   BatchWords *bw_host = nullptr, *bw_dev = nullptr;  // the batched step's per-row words (pinned, device)
+  // weight-only mode's single-token step: slot 0's cache bases {kcache, vcache} on the device, the
+  // one-row AttnRows of its k_attn_decode_batch (written when the scratch is allocated)
+  float **w4_kv = nullptr;
+  unsigned w4_gen = 0;  // vsim_w4a16_set_step's count of changes when the step graphs were last checked
   int kernels_last = 0;
 
   // fused single-token decode step (layer.hip) and its graphs
@@ -269,6 +273,7 @@ std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   add(&m->logit_host, V * f, S_PINNED);
   add(&m->bw_host, sizeof(BatchWords), S_PINNED);
   add(&m->bw_dev, sizeof(BatchWords));
+  add(&m->w4_kv, 2 * sizeof(float *));
   add(&m->xqa, q4(E), S_POISON);
   add(&m->xda, n * E * f, S_POISON);
   add(&m->inpL2, E * f, S_POISON);
@@ -337,6 +342,8 @@ int ensure_scratch(vsim_model *m, int N) {
     if (b.flags & S_ZERO) VSIM_HIP(hipMemset(*b.p, 0, b.bytes));
   }
   m->tw = tail_ws_carve(m->tail_ws, E_(m));
+  float *const kv[2] = {m->kcache, m->vcache};
+  VSIM_HIP(hipMemcpy(m->w4_kv, kv, sizeof(kv), hipMemcpyHostToDevice));
   m->n_max = n;
   return VSIM_OK;
 }
@@ -1218,6 +1225,112 @@ struct DecodeStep {
   }
 };
 
+// Weight-only mode's single-token step (w4a16_decode.hip), in enqueue_decode's replayable form: the
+// position comes from npast_dev.  Every launch gives the bits of the general path's kernels on the
+// same row (run_layer at N = 1), so the logits and the cache rows are eval_seq's.  Per layer:
+//   parallel residual (GPT-J, GPT-NeoX), 7 launches:
+//     1. k_w4a16_ln       the input norm (+ GPT-NeoX's post-attention norm of the same row) -> operands
+//     2. k_gemv_w4a16     {Q, K, V, fc_in}
+//     3. k_attn_decode_batch at one row: RoPE, the cache write, KQ, softmax, KQV -> the f32 row
+//     4. k_w4a16_rows     the attention row's operand (its maximum runs across the heads)
+//     5. k_gemv_w4a16     {out-projection}
+//     6. k_w4a16_gelu     fc_in's row + bias -> GELU -> operand
+//     7. k_gemv_w4a16     {fc_out}, joining inpL = inpL + (attn + ff) in place
+//   serial residual (GPT-NeoX with use_parallel_residual = 0, BLOOM), 9 launches: 1 with one norm, 2
+//     without fc_in, 3, 4, 5 joining cur2 = attn + inpL, then k_w4a16_ln of cur2 with the
+//     post-attention norm, k_gemv_w4a16 {fc_in}, 6, and 7 joining ff + inpL (BLOOM: + cur2) into inpL.
+//   head, 2 launches: k_w4a16_ln with the final norm, k_gemv_w4a16 {lm_head (+ GPT-J's bias)}.
+// Process-wide switch (vsim_w4a16_set_step) and the shapes the step takes: k_attn_decode_batch's
+// (head dim a multiple of 32 up to 256, its LDS row for n_ctx scores) and k_w4a16_ln's row in LDS.
+std::atomic<int> g_w4a16_step{1};
+std::atomic<unsigned> g_w4a16_gen{0};  // changes of the switch: a model drops its step graphs after one
+
+bool w4a16_step_ok(const vsim_model *m) {
+  const int E = m->hp.n_embd, d = E / m->hp.n_head;
+  return d % 32 == 0 && d <= 256 && (size_t)E * 4 <= 64 * 1024 &&
+         (size_t)attn_lds_floats(d, m->n_ctx) * sizeof(float) <= 160 * 1024;
+}
+// weight-only mode on the general path for its single-token calls too (switched off, or a shape
+// the step does not take): uncaptured, one host round trip per token
+bool w4a16_general(const vsim_model *m) {
+  return m->mode == VSIM_MODE_W4A16 && !(g_w4a16_step.load() && w4a16_step_ok(m));
+}
+
+int enqueue_decode_w4a16(vsim_model *m, int &nk) {
+  const int E = m->hp.n_embd, F = 4 * E, V = m->hp.n_vocab;
+  const GraphDesc &G = m->gd;
+  hipStream_t s = m->stream;
+  DevTables tab;
+  RC(tables_get(&tab));
+  // a row operand: halves where the exact step keeps a row's factors, the exponent where it keeps
+  // the nibbles (as the general path's products use the same buffers)
+  struct Operand {
+    _Float16 *h;
+    int32_t *e;
+  };
+  const Operand x1{(_Float16 *)m->xd1, (int32_t *)m->xq1}, x2{(_Float16 *)m->xd2, (int32_t *)m->xq2},
+      x3{(_Float16 *)m->xd3, (int32_t *)m->xq3}, xa{(_Float16 *)m->xda, (int32_t *)m->xqa};
+  const bool serial = G.residual != RES_PARALLEL, keep_joined = G.residual == RES_SERIAL_JOINED;
+  const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
+  auto job = [&](const void *w, int M, int K, const Operand &x, const float *bias, float *y, const float *res = nullptr,
+                 const float *res_a = nullptr) {
+    return W4a16GemvJob{w4_view(w, M, K), x.h, x.e, bias, res, res_a, y};
+  };
+  auto ln = [&](const float *x, const float *w1, const float *b1, const Operand &o1, const float *w2, const float *b2,
+                const Operand &o2) {
+    const W4a16Ln A{x, E, w1, b1, o1.h, o1.e, w2, b2, w2 ? o2.h : nullptr, w2 ? o2.e : nullptr};
+    LAUNCH(m, nk, launch_w4a16_ln(A, s), "k_w4a16_ln", 4.0 * E * (w2 ? 5 : 3) + 2.0 * E * (w2 ? 2 : 1));
+    return VSIM_OK;
+  };
+  auto gemv = [&](std::initializer_list<W4a16GemvJob> jobs, const char *what) {
+    W4a16Gemv B{};
+    double bytes = 0.0;
+    for (const W4a16GemvJob &j : jobs) {
+      B.j[B.nj++] = j;
+      bytes += w4_algo_bytes(j.w);
+    }
+    LAUNCH(m, nk, launch_w4a16_gemv(B, s), std::string("k_gemv_w4a16 (") + what + ")", bytes);
+    return VSIM_OK;
+  };
+  for (int il = m->l0; il < m->l1; ++il) {
+    const LayerW &L = m->layers[il - m->l0];
+    const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
+    const float *bq = G.qkvo_bias ? L.bq : nullptr, *bk = G.qkvo_bias ? L.bk : nullptr,
+                *bv = G.qkvo_bias ? L.bv : nullptr, *bo = G.qkvo_bias ? L.bo : nullptr;
+    const bool two_here = G.two_norms && !serial;  // both norms read the same row
+    RC(ln(m->inpL, L.ln1_w, L.ln1_b, x1, two_here ? L.ln2_w : nullptr, two_here ? L.ln2_b : nullptr, x2));
+    const W4a16GemvJob q = job(L.wq, E, E, x1, bq, m->Qb), k = job(L.wk, E, E, x1, bk, m->Kb),
+                       v = job(L.wv, E, E, x1, bv, m->Vb);
+    // fc_in's bias goes with the GELU
+    if (serial)
+      RC(gemv({q, k, v}, "Q, K, V"));
+    else
+      RC(gemv({q, k, v, job(L.wfc, F, E, two_here ? x2 : x1, nullptr, m->fch)}, "Q, K, V, fc_in"));
+    // (the attention's Q4 row goes where the f32 row's operand follows it)
+    AttnJob A = attn_job(decode_attn_desc(m, tab, ActRow{q4_rows(m->xqa, E), m->xda}, 1), nullptr, nullptr, nullptr);
+    A.out = m->attn_in;
+    const AttnRows R{m->w4_kv, m->w4_kv + 1, loff, m->npast_dev};
+    LAUNCH(m, nk, launch_attn_decode_batch(A, R, 1, m->n_ctx, s), "k_attn_decode_batch", kv_bytes);
+    LAUNCH(m, nk, launch_w4a16_rows(m->attn_in, E, 1, xa.h, xa.e, s), "k_w4a16_rows", (double)E * 6);
+    if (serial) {
+      // cur2 = attn + inpL, the MLP's input (BLOOM: and the residual)
+      RC(gemv({job(L.wo, E, E, xa, bo, m->cur2, m->inpL)}, "out-proj"));
+      RC(ln(m->cur2, L.ln2_w, L.ln2_b, x2, nullptr, nullptr, x2));
+      RC(gemv({job(L.wfc, F, E, x2, nullptr, m->fch)}, "fc_in"));
+    } else {
+      RC(gemv({job(L.wo, E, E, xa, bo, m->attn)}, "out-proj"));
+    }
+    LAUNCH(m, nk, launch_w4a16_gelu(m->fch, L.bfc, F, x3.h, x3.e, nullptr, s), "k_w4a16_gelu", (double)F * 10);
+    // the layer's join in fc_out's epilogue (k_add_residual's orders; BLOOM: ff + the joined row)
+    RC(gemv({job(L.wproj, E, F, x3, L.bproj, m->inpL, keep_joined ? m->cur2 : m->inpL, serial ? nullptr : m->attn)},
+            "fc_out"));
+  }
+  RC(ln(m->inpL, m->lnf_w, m->lnf_b, x1, nullptr, nullptr, x1));
+  RC(gemv({job(m->lmh, V, E, x1, G.lmh_bias ? m->lmh_b : nullptr, m->logits)}, "lm_head"));
+  m->resid_final = m->inpL;
+  return VSIM_OK;
+}
+
 int enqueue_decode(vsim_model *m, int &nk) {
   if (m->mode == VSIM_MODE_FAST && fast_decode_ok(m)) return enqueue_decode_fast(m, nk);
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
@@ -1232,6 +1345,7 @@ int enqueue_decode(vsim_model *m, int &nk) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
   }
+  if (m->mode == VSIM_MODE_W4A16) return enqueue_decode_w4a16(m, nk);  // (a whole model: set_mode)
   DecodeStep S(m, nk, tab);
   for (int il = m->l0; il < m->l1; ++il)
     RC(m->gd.residual != RES_PARALLEL ? S.layer_serial(il) : S.layer_parallel(il));
@@ -1782,6 +1896,12 @@ int vsim_model_set_mode(vsim_model *m, int mode) {
   return VSIM_OK;
 }
 
+int vsim_w4a16_set_step(int enable) {
+  const int on = enable ? 1 : 0, old = g_w4a16_step.exchange(on);
+  if (old != on) ++g_w4a16_gen;
+  return old;
+}
+
 int vsim_model_set_graph(vsim_model *m, int enable) {
   m->graph_enabled = enable != 0;
   return VSIM_OK;
@@ -1881,6 +2001,10 @@ int enqueue_step(vsim_model *m, StepKind kind, int &nk, bool want_logits = true,
 // Capture (once per kind and mode) the whole step as a hipGraph.
 int decode_graph(vsim_model *m, StepKind kind) {
   StepGraph &g = m->step[kind];
+  if (const unsigned gen = g_w4a16_gen.load(); gen != m->w4_gen) {  // vsim_w4a16_set_step since the last look
+    for (StepGraph &o : m->step) drop(o);
+    m->w4_gen = gen;
+  }
   if (g.exec && g.mode == m->mode) return VSIM_OK;
   drop(g);
   VSIM_HIP(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
@@ -1962,7 +2086,7 @@ int run_last_row_head(vsim_model *m, const BatchDesc &D, int &nk) {
 }
 
 // A single-token step on the general path on slot 0, uncaptured: what the whole-model single-token
-// calls (eval_argmax, generate, eval_sample) run in weight-only mode, which has no decode graph yet.
+// calls (eval_argmax, generate, eval_sample) run in weight-only mode without its step (w4a16_general).
 // The logits row ends in m->logits.
 int enqueue_single_general(vsim_model *m, const char *who, int n_past, int32_t token, int &nk) {
   const BatchDesc D{.kind = BatchKind::PROMPT, .N = 1, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
@@ -2046,7 +2170,7 @@ int vsim_model_eval_argmax(vsim_model *m, int n_past, int32_t token, int32_t *ne
   RC(begin_single(m, "eval_argmax", n_past, 1, "1", token));
   const ErrScope es(m);
   int nk = 0;
-  if (m->mode == VSIM_MODE_W4A16) {
+  if (w4a16_general(m)) {
     RC(enqueue_single_general(m, "eval_argmax", n_past, token, nk));
     RC(launch_argmax(m->logits, m->hp.n_vocab, m->am_dev, m->am_ws, m->stream));
     ++nk;
@@ -2064,7 +2188,7 @@ int vsim_model_generate(vsim_model *m, int n_past, int32_t token, int n_steps, i
   RC(begin_single(m, "generate", n_past, n_steps, "n_steps", token));
   if (n_steps == 0) return VSIM_OK;
   const ErrScope es(m);
-  if (m->mode == VSIM_MODE_W4A16) {  // one general-path step and one host round trip per token
+  if (w4a16_general(m)) {  // one general-path step and one host round trip per token
     for (int i = 0; i < n_steps; ++i) {
       int nk = 0;
       RC(enqueue_single_general(m, "generate", n_past + i, token, nk));
@@ -2101,7 +2225,7 @@ int vsim_model_eval_sample(vsim_model *m, vsim_sampler *sm, int n_past, int32_t 
   const ErrScope es(m);
   fill_topk_params(m->sp_host, sm, true);
   int nk = 0;
-  if (m->mode == VSIM_MODE_W4A16) {
+  if (w4a16_general(m)) {
     hipStream_t s = m->stream;
     VSIM_HIP(hipMemcpyAsync(m->sp_dev, m->sp_host, sizeof(TopkParams), hipMemcpyHostToDevice, s));
     RC(enqueue_single_general(m, "eval_sample", n_past, token, nk));
@@ -2159,7 +2283,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
   const int E = m->hp.n_embd, V = m->hp.n_vocab;
   hipStream_t s = m->stream;
   int nk = 0;
-  if (N == 1 && m->mode != VSIM_MODE_W4A16) {  // every graph has a single-token step (the serial-residual ones with 6 launches per layer)
+  if (N == 1 && !w4a16_general(m)) {  // every graph has a single-token step (the serial-residual ones with 6 launches per layer)
     if (m->first) {
       if (!tokens) { set_error("eval: first stage needs tokens"); return VSIM_EINVAL; }
       if (tokens[0] < 0 || tokens[0] >= V) { set_error("eval: token id out of range"); return VSIM_EINVAL; }
@@ -2173,7 +2297,7 @@ int vsim_model_eval(vsim_model *m, int n_past, const int32_t *tokens, int N, con
     // (the graph is the whole model's step: a partial stage, with its residual in and out, runs eagerly)
     RC(run_step(m, STEP_LOGITS, m->graph_enabled && m->first && m->last, nk, logits != nullptr, resid_out));
   } else {
-    // general path: prompt batches (N > 1), and every eval of weight-only mode
+    // general path: prompt batches (N > 1), and weight-only mode's evals without its step
     const BatchDesc D{.kind = BatchKind::PROMPT, .N = N, .n_past = n_past, .kcache = m->kcache, .vcache = m->vcache,
                       .mode = m->mode, .who = "eval"};
     RC(enqueue_prompt(m, D, tokens, resid_in, nk));

@@ -61,6 +61,7 @@ EXPORTS = [
     "vsim_op_w4a16_rows", "vsim_op_q4_gemm_w4a16_rows", "vsim_model_decode_batch_w4a16",
     "vsim_model_decode_batch_sample_w4a16",
     "vsim_op_ln_quant", "vsim_op_gemv_batch",
+    "vsim_op_w4a16_ln", "vsim_op_w4a16_gelu", "vsim_op_w4a16_gemv", "vsim_w4a16_set_step",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -201,6 +202,25 @@ class GemvBatchJob(ctypes.Structure):
 class GemvBatchArgs(ctypes.Structure):
     """vsim_gemv_batch_args (include/vsim_hip.h)."""
     _fields_ = [("j", GemvBatchJob * 4), ("nj", ctypes.c_int32)]
+
+
+class W4a16LnArgs(ctypes.Structure):
+    """vsim_w4a16_ln_args (include/vsim_hip.h)."""
+    _fields_ = [("x", ctypes.c_void_p), ("n", ctypes.c_int32), ("w1", ctypes.c_void_p), ("b1", ctypes.c_void_p),
+                ("x16_1", ctypes.c_void_p), ("e1", ctypes.c_void_p), ("w2", ctypes.c_void_p), ("b2", ctypes.c_void_p),
+                ("x16_2", ctypes.c_void_p), ("e2", ctypes.c_void_p)]
+
+
+class W4a16GemvJob(ctypes.Structure):
+    """vsim_w4a16_gemv_job (include/vsim_hip.h)."""
+    _fields_ = [("w", ctypes.c_void_p), ("M", ctypes.c_int32), ("K", ctypes.c_int32), ("x16", ctypes.c_void_p),
+                ("e", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("res", ctypes.c_void_p),
+                ("res_a", ctypes.c_void_p), ("y", ctypes.c_void_p)]
+
+
+class W4a16GemvArgs(ctypes.Structure):
+    """vsim_w4a16_gemv_args (include/vsim_hip.h)."""
+    _fields_ = [("j", W4a16GemvJob * 4), ("nj", ctypes.c_int32)]
 
 
 class QuantizeStats(ctypes.Structure):
@@ -345,6 +365,10 @@ def lib():
     L.vsim_model_decode_batch_w4a16.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     L.vsim_model_decode_batch_sample_w4a16.argtypes = [vp, ci, vp, vp, vp, ctypes.POINTER(vp), vp]
     L.vsim_op_ln_quant.argtypes = [ctypes.POINTER(LnQuantArgs), vp]
+    L.vsim_op_w4a16_ln.argtypes = [ctypes.POINTER(W4a16LnArgs), vp]
+    L.vsim_op_w4a16_gelu.argtypes = [vp, vp, ci, vp, vp, vp, vp]
+    L.vsim_op_w4a16_gemv.argtypes = [ctypes.POINTER(W4a16GemvArgs), vp]
+    L.vsim_w4a16_set_step.argtypes = [ci]
     L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
     _lib = L
     return L
@@ -517,6 +541,45 @@ def q4_gemm_w4a16_rows(w, M, K, x16, e, n, bias, y, stream=None):
     not synchronized."""
     check(lib().vsim_op_q4_gemm_w4a16_rows(ptr(w), M, K, ptr(x16), ptr(e), n, ptr(bias), ptr(y), stream),
           "q4_gemm_w4a16_rows")
+
+
+def w4a16_ln(x, n, w1, b1, x16_1, e1, w2=None, b2=None, x16_2=None, e2=None, stream=None):
+    """vsim_op_w4a16_ln on device buffers (torch tensors or None): the LayerNorm of the row x [n] with
+    (w1, b1) straight to w4a16_rows' operand (x16_1, e1) of the normalized row, and with (w2, b2) to
+    (x16_2, e2) when given; the bits of norm followed by w4a16_rows.  Enqueued on `stream`, not
+    synchronized."""
+    a = W4a16LnArgs(ptr(x), int(n), ptr(w1), ptr(b1), ptr(x16_1), ptr(e1), ptr(w2), ptr(b2), ptr(x16_2), ptr(e2))
+    check(lib().vsim_op_w4a16_ln(ctypes.byref(a), stream), "w4a16_ln")
+
+
+def w4a16_gelu(x, bias, K, x16, e, g=None, stream=None):
+    """vsim_op_w4a16_gelu on device buffers (torch tensors or None): g = gelu(x + bias) of the row x [K]
+    by the fp16 table, then w4a16_rows' operand (x16, e) of g; g [K] f32 also stored when given.
+    Enqueued on `stream`, not synchronized."""
+    check(lib().vsim_op_w4a16_gelu(ptr(x), ptr(bias), int(K), ptr(x16), ptr(e), ptr(g), stream), "w4a16_gelu")
+
+
+def w4a16_gemv_args(jobs):
+    """vsim_w4a16_gemv_args from jobs = [(w, M, K, x16, e, bias, res, res_a, y)], torch tensors or None."""
+    a = W4a16GemvArgs()
+    a.nj = len(jobs)
+    for i, (w, M, K, x16, e, bias, res, res_a, y) in enumerate(jobs[:4]):
+        a.j[i] = W4a16GemvJob(ptr(w), int(M), int(K), ptr(x16), ptr(e), ptr(bias), ptr(res), ptr(res_a), ptr(y))
+    return a
+
+
+def w4a16_gemv(jobs, stream=None):
+    """vsim_op_w4a16_gemv on jobs (w4a16_gemv_args): up to four single-row products of W4T32 weights
+    with w4a16_rows operands in one launch, each q4_gemm_w4a16_rows' bits at n = 1, then y = v,
+    v + res or res + (res_a + v).  Enqueued on `stream`, not synchronized."""
+    a = jobs if isinstance(jobs, W4a16GemvArgs) else w4a16_gemv_args(jobs)
+    check(lib().vsim_op_w4a16_gemv(ctypes.byref(a), stream), "w4a16_gemv")
+
+
+def w4a16_set_step(enable) -> int:
+    """Weight-only mode's single-token step on (default) or off (every single-token call on the
+    general path); same bits either way.  Process-wide; returns the previous setting."""
+    return int(lib().vsim_w4a16_set_step(int(enable)))
 
 
 def batch_set_fast_gemm(enable) -> int:
