@@ -191,8 +191,11 @@ int vsim_op_w4a16_ln(const vsim_w4a16_ln_args *a, void *stream) {
   if (!a) { set_error("w4a16_ln: null argument"); return VSIM_EINVAL; }
   DevTables tab;  // (the device's LayerNorm counters come with its tables)
   RC(tables_get(&tab));
-  return launch_w4a16_ln(W4a16Ln{a->x, a->n, a->w1, a->b1, (_Float16 *)a->x16_1, a->e1, a->w2, a->b2,
-                                 (_Float16 *)a->x16_2, a->e2},
+  // a second norm given in part goes through as it is, for the launcher to refuse
+  const NormRow n2{a->w2, a->b2};
+  const bool two = a->w2 || a->b2 || a->x16_2 || a->e2;
+  const W4a16Operand o1{(_Float16 *)a->x16_1, a->e1}, o2{(_Float16 *)a->x16_2, a->e2};
+  return launch_w4a16_ln(w4a16_ln_job(a->x, a->n, NormRow{a->w1, a->b1}, o1, two ? &n2 : nullptr, o2),
                          (hipStream_t)stream);
 }
 int vsim_op_w4a16_gelu(const float *x, const float *bias, int K, void *x16, int32_t *e, float *g_or_null,
@@ -202,14 +205,13 @@ int vsim_op_w4a16_gelu(const float *x, const float *bias, int K, void *x16, int3
 int vsim_op_w4a16_gemv(const vsim_w4a16_gemv_args *a, void *stream) {
   if (!a || a->nj < 1 || a->nj > 4) { set_error("w4a16_gemv: 1..4 jobs"); return VSIM_EINVAL; }
   W4a16Gemv B{};
-  B.nj = a->nj;
   for (int i = 0; i < a->nj; ++i) {
     const vsim_w4a16_gemv_job &j = a->j[i];
     if (!j.w || j.M <= 0 || j.K <= 0 || j.K % QK) {
       set_error("w4a16_gemv: every job needs K a positive multiple of 32, M > 0, w, x16, e and y");
       return VSIM_EINVAL;
     }
-    B.j[i] = W4a16GemvJob{w4_view(j.w, j.M, j.K), (const _Float16 *)j.x16, j.e, j.bias, j.res, j.res_a, j.y};
+    B.j[B.nj++] = w4a16_gemv_job(j.w, j.M, j.K, {(_Float16 *)j.x16, (int32_t *)j.e}, j.bias, j.y, j.res, j.res_a);
   }
   return launch_w4a16_gemv(B, (hipStream_t)stream);
 }
@@ -601,8 +603,8 @@ int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
   if (!a || a->nj < 1 || a->nj > 4) { set_error("fast_gemv: 1 to 4 jobs"); return VSIM_EINVAL; }
   const int K = a->j[0].k;
   if (K <= 0 || K % QK) { set_error("fast_gemv: k must be a positive multiple of 32"); return VSIM_EINVAL; }
-  FastGemv P{};
-  P.nj = a->nj;
+  FastJob jobs[4];
+  Q4Rows gelu_out;  // the GELU job's output row has `rows` values
   bool rope = false, pos = false;
   for (int i = 0; i < a->nj; ++i) {
     const vsim_fast_job &j = a->j[i];
@@ -615,11 +617,8 @@ int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
     }
     rope |= j.epi == FE_ROPE_Q || j.epi == FE_ROPE_K;
     pos |= j.epi >= FE_ROPE_Q;
-    if (j.epi == FE_GELU_Q) {
-      P.oq_qs = q4_rows(a->oq, j.rows).qs;
-      P.oq_d = q4_rows(a->oq, j.rows).d;
-    }
-    P.j[i] = FastJob{w4_view(j.w, j.rows, j.k), j.bias, j.y, j.epi, j.act};
+    if (j.epi == FE_GELU_Q) gelu_out = q4_rows(a->oq, j.rows);
+    jobs[i] = fast_job(j.w, j.rows, j.k, j.bias, j.y, j.epi, j.act);
   }
   if (pos && !a->n_past) { set_error("fast_gemv: n_past missing"); return VSIM_EINVAL; }
   if (rope && (!a->cs || a->d <= 0 || a->n_rot <= 0 || a->n_rot % 2 || a->n_rot > a->d || (a->style != 0 && a->style != 1) ||
@@ -628,25 +627,15 @@ int vsim_op_fast_gemv(const vsim_fast_gemv_args *a, void *stream) {
     return VSIM_EINVAL;
   }
   if (a->clear && a->nclear < 0) { set_error("fast_gemv: nclear < 0"); return VSIM_EINVAL; }
-  for (int i = 0; i < 2; ++i) {
-    const Q4Rows x = a->lnx || !a->xq[i] ? Q4Rows{} : q4_rows(a->xq[i], K);
-    P.xq[i] = x.qs;
-    P.xd[i] = x.d;
-    P.lnw[i] = a->lnw[i];
-    P.lnb[i] = a->lnb[i];
-  }
-  P.lnx = a->lnx;
   DevTables tab;
   RC(tables_get(&tab));
-  P.gelu_tab = tab.gelu_f16;
-  P.npast = a->n_past;
-  P.cs = (const double2 *)a->cs;
-  P.d = rope ? a->d : 1;
-  P.n_rot = a->n_rot;
-  P.style = a->style;
-  P.clear = a->clear;
-  P.nclear = a->clear ? a->nclear : 0;
-  return launch_fast_gemv(P, K, (hipStream_t)stream);
+  auto row = [&](const void *xq) { return xq ? q4_rows(xq, K) : Q4Rows{}; };
+  const FastAct act{.lnx = a->lnx,
+                    .n = {NormRow{a->lnw[0], a->lnb[0]}, NormRow{a->lnw[1], a->lnb[1]}},
+                    .x = {row(a->xq[0]), row(a->xq[1])}};
+  const FastPos at{a->n_past, (const double2 *)a->cs, a->d, a->n_rot, a->style};
+  return launch_fast_gemv(fast_gemv(act, jobs, a->nj, tab.gelu_f16, gelu_out, at, a->clear, a->nclear), K,
+                          (hipStream_t)stream);
 }
 
 int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream) {
@@ -659,24 +648,10 @@ int vsim_op_fast_tail(const vsim_fast_tail_args *a, void *stream) {
     set_error("fast_tail: bad shape (whole 32-row tiles, k a multiple of 32, 1 <= sf <= 8)");
     return VSIM_EINVAL;
   }
-  FastTail T{};
-  T.wf = w4_view(a->wf, a->rows, a->k);
-  T.xf_qs = q4_rows(a->xf, a->k).qs;
-  T.xf_d = q4_rows(a->xf, a->k).d;
-  T.ffp = a->ffp;
-  T.sf = a->sf;
-  T.q = a->q;
-  T.kc = a->kc;
-  T.vc = a->vc;
-  T.npast = a->n_past;
-  T.d = a->d;
-  T.H = a->H;
-  T.nchunk = a->nchunk;
-  T.scale = a->scale;
-  T.part = a->part;
-  T.hcnt = a->hcnt;
-  T.oq_qs = q4_rows(a->oq, a->d * a->H).qs;
-  T.oq_d = q4_rows(a->oq, a->d * a->H).d;
+  const FastTail T = fast_tail_job(
+      w4_view(a->wf, a->rows, a->k), q4_rows(a->xf, a->k), a->ffp, a->sf,
+      FastAttn{.q = a->q, .kc = a->kc, .vc = a->vc, .npast = a->n_past, .d = a->d, .H = a->H, .nchunk = a->nchunk,
+               .scale = a->scale, .part = a->part, .hcnt = a->hcnt, .o = q4_rows(a->oq, a->d * a->H)});
   // the per-head counters are this call's (the model zeroes them from the layer's GEMV launch)
   VSIM_HIP(hipMemsetAsync(a->hcnt, 0, (size_t)4 * a->H * sizeof(unsigned), (hipStream_t)stream));
   return launch_fast_tail(T, (hipStream_t)stream);
@@ -688,17 +663,8 @@ int vsim_op_fast_oproj_join(const void *w, int E, const void *xq, const float *b
     set_error("fast_oproj_join: bad argument");
     return VSIM_EINVAL;
   }
-  FastOproj O{};
-  O.w = w4_view(w, E, E);
-  O.xq = q4_rows(xq, E).qs;
-  O.xd = q4_rows(xq, E).d;
-  O.bo = bo;
-  O.ffp = ffp;
-  O.sf = sf;
-  O.bproj = bproj;
-  O.x = x;
-  O.out = out;
-  return launch_fast_oproj_join(O, (hipStream_t)stream);
+  return launch_fast_oproj_join(fast_oproj_job(w4_view(w, E, E), q4_rows(xq, E), bo, ffp, sf, bproj, x, out),
+                                (hipStream_t)stream);
 }
 int vsim_op_tables(uint16_t *exp_f16_host, uint16_t *gelu_f16_host) { return tables_host(exp_f16_host, gelu_f16_host); }
 int vsim_gemm_set_streamk(int enable) { return gemm_set_streamk(enable); }

@@ -1,5 +1,12 @@
 // vsim_amd/csrc/fast.hpp — parameter blocks and launchers of the fast-mode decode step
-// (fast_decode.hip), shared with the model executor (model.cpp).
+// (fast_decode.hip), shared with the model executor (model.cpp) and the op entries (capi.cpp),
+// which fill them through decode_jobs.hpp.  Three launches per layer and one for the head:
+//   K1  k_fast_gemv        FastGemv: LayerNorm(s) in the prologue, {fc_in + GELU, Q, K, V}; the head
+//                          is the same kernel with the final norm and the lm_head as its one job
+//   K2  k_fast_tail        FastTail: fc_out split over K beside the attention chunks; the chunk
+//                          workgroup of a head that finishes last merges that head's chunks
+//   K3  k_fast_oproj_join  FastOproj: out-projection of the merged row, fc_out's partial rows summed,
+//                          the residual join
 #pragma once
 
 #include "common.hpp"
@@ -13,8 +20,8 @@ constexpr int FD_U = 4;              // 16-byte weight loads in flight per lane 
 constexpr int FD_MAXE = 8192;        // largest n_embd / activation length handled
 constexpr int FD_CHUNK = 64;         // attention positions per chunk workgroup
 constexpr int FD_MAXCH = 64;         // chunks per head the merge handles (n_ctx <= 4096)
-constexpr int FD_SF = 2;
-constexpr size_t FD_PAD = 64 << 10;  // readable slack after the weight arena (TileStream)             // fc_out K splits (partial rows summed by K3)
+constexpr int FD_SF = 2;             // fc_out K splits (partial rows summed by K3)
+constexpr size_t FD_PAD = 64 << 10;  // readable slack after the weight arena (TileStream)
 // GEMV epilogues: store (+bias); fc_in bias + GELU + quantize; Q with RoPE; K with RoPE
 // into the KV cache at n_past; V into the cache at n_past
 enum { FE_STORE = 0, FE_GELU_Q = 1, FE_ROPE_Q = 2, FE_ROPE_K = 3, FE_V = 4 };
@@ -26,15 +33,6 @@ struct FastJob {
                       // cache [n_ctx][E] (row n_past is written)
   int epi;
   int act;            // which activation row (FastGemv::xq/xd) feeds this job (0 or 1)
-};
-
-// LayerNorm(s) of the joined residual row, quantized into Q4 SoA activation rows
-struct FastLn {
-  const float *x;                   // residual row [E]
-  const float *w[2], *b[2];         // affine of each LayerNorm
-  uint8_t *qs[2];                   // output activation i: nibble plane [E/32][16] ...
-  float *d[2];                      // ... and scales [E/32]
-  int n, E;                         // n = 1 or 2 LayerNorms
 };
 
 // K1: a batch of GEMVs over the same-K activations (Q4 SoA, chosen per job by `act`)
@@ -84,7 +82,6 @@ struct FastOproj {
   W4 w;                    // out-projection E x E
   const uint8_t *xq;       // merged attention output, Q4 SoA (FastTail::oq_qs / oq_d)
   const float *xd;
-  int d;
   const float *bo;         // may be null (GPT-J)
   const float *ffp;        // [sf][E]
   int sf;
@@ -93,7 +90,6 @@ struct FastOproj {
   float *out;              // residual out
 };
 
-int launch_fast_ln(const FastLn &P, hipStream_t s);
 int launch_fast_gemv(const FastGemv &P, int E, hipStream_t s);
 int launch_fast_tail(const FastTail &A, hipStream_t s);
 int launch_fast_oproj_join(const FastOproj &P, hipStream_t s);

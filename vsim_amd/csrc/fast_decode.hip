@@ -5,22 +5,24 @@
 // (activations re-quantized with quantize_row_q4_0 semantics, ggml.c:209-251), but sums
 // each Q4_0 block with the integer dot v_dot8_i32_i4 and accumulates in any order, so it is
 // HBM-bound rather than bound by the reference's sequential fp32 chain.  It is not
-// bit-exact.  One layer = 4 launches:
+// bit-exact.  One layer = 3 launches:
 //
-//   k_fast_ln          LayerNorm(s) of the joined residual (ggml.c:4246-4304 + the affine,
-//                      vsim.cpp:525-532), quantized (ggml.c:209-251)
-//   k_fast_gemv        32-row tiles of {fc_in (+bias, GELU, quantize into fc_out's
-//                      activation), Q, K, V}
-//   k_fast_tail        fc_out split over K (FD_SF partial rows, summed in a fixed order by
+//   k_fast_gemv        in every workgroup's prologue the LayerNorm(s) of the residual row
+//                      (ggml.c:4246-4304 + the affine, vsim.cpp:525-532), quantized
+//                      (ggml.c:209-251) into LDS; then 32-row tiles of {fc_in (+bias, GELU,
+//                      quantize into fc_out's activation), Q and K with RoPE
+//                      (ggml.c:6086-6153 / 5919-5974), V}, K and V straight into the cache
+//   k_fast_tail        fc_out split over K (fast_sf partial rows, summed in a fixed order by
 //                      the next kernel) beside flash-decoding attention: each (head,
-//                      64-position chunk) workgroup does RoPE (ggml.c:6086-6153 /
-//                      5919-5974), the KV write, KQ, a chunk softmax and KQV
-//   k_fast_oproj_join  merges the attention chunks and quantizes the attention output in
-//                      every workgroup, then the out-projection and the residual join
+//                      64-position chunk) workgroup does KQ, a chunk softmax and KQV; the
+//                      chunk workgroup that counts last for its head merges the head's chunks
+//                      and quantizes the attention output
+//   k_fast_oproj_join  the out-projection of that row and the residual join
 //                      inpL + ((attn + b_o) + (ff + b_proj)) (vsim.cpp:694-695)
 //
-// The head (final LayerNorm + lm_head) is k_fast_ln + k_fast_gemv.  n_past is read from
-// device memory, so the step is captured once in a hipGraph and replayed for every position.
+// The head (final LayerNorm + lm_head) is one k_fast_gemv with the norm in its prologue.
+// n_past is read from device memory, so the step is captured once in a hipGraph and replayed
+// for every position.
 #include <cstdlib>
 
 #include "fast.hpp"
@@ -203,72 +205,11 @@ struct ActStage {
 // ggml_compute_forward_norm_f32 (ggml.c:4246-4304): mean and variance in double,
 // y = (float)(x - mean) * (float)(1/sqrt(var + eps)), then w*y + b in float
 // (vsim.cpp:525-532), then quantize_row_q4_0.  Fast mode takes both moments in one pass
-// (var = E[x^2] - mean^2 in double: one block reduction).  LN_SPLIT workgroups per
-// LayerNorm: each reads the whole row for the moments (16 KB from L2 for E = 4096) and
-// normalizes and quantizes one slice of it, so the per-element phase runs on LN_SPLIT CUs.
-constexpr int LN_NT = 256, LN_SPLIT = 8;
-__global__ void __launch_bounds__(LN_NT) k_fast_ln(FastLn P) {
-  constexpr int MAXPER = FD_MAXE / (4 * LN_NT);  // float4 per thread
-  __shared__ double red[2 * (LN_NT / 64)];
-  const int tid = threadIdx.x, wid = tid >> 6, E = P.E;
-  const int l = blockIdx.x / LN_SPLIT, part = blockIdx.x % LN_SPLIT;
-  const float *__restrict__ w = P.w[l];
-  const float *__restrict__ bb = P.b[l];
-  const int nb = E / QK;
-  const int b0 = part * nb / LN_SPLIT, b1 = (part + 1) * nb / LN_SPLIT;  // this slice's blocks
-  constexpr int MAXS = FD_MAXE / LN_SPLIT / LN_NT;  // slice elements per thread
-  float xi[MAXS], wi[MAXS], bi[MAXS];
-#pragma unroll
-  for (int k = 0; k < MAXS; ++k) {
-    const int i = b0 * QK + tid + LN_NT * k;
-    const bool mine = i < b1 * QK;
-    xi[k] = mine ? P.x[i] : 0.0f;
-    wi[k] = mine ? w[i] : 0.0f;
-    bi[k] = mine ? bb[i] : 0.0f;
-  }
-  double s = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < MAXPER; ++k) {
-    const int e = 4 * (tid + LN_NT * k);
-    if (e < E) {
-      const float4 v = *(const float4 *)(P.x + e);
-      s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-      s2 += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-    }
-  }
-  s = wave_sum_d(s);
-  s2 = wave_sum_d(s2);
-  if ((tid & 63) == 0) {
-    red[2 * wid] = s;
-    red[2 * wid + 1] = s2;
-  }
-  __syncthreads();
-  s = 0.0;
-  s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < LN_NT / 64; ++k) {
-    s += red[2 * k];
-    s2 += red[2 * k + 1];
-  }
-  const double mean = s / E;
-  const double var = s2 / E - mean * mean;
-  const float scale = (float)(1.0 / sqrt(var + (double)1e-5f));
-#pragma unroll
-  for (int k = 0; k < MAXS; ++k) {
-    const int i0 = b0 * QK + LN_NT * k;
-    if (i0 >= b1 * QK) break;
-    const int i = i0 + tid;
-    const bool ok = i0 + (tid & ~31) < b1 * QK;  // half-wave uniform
-    const float y = ok ? wi[k] * ((float)((double)xi[k] - mean) * scale) + bi[k] : 0.0f;
-    const int blk = ok ? i / QK : 0;
-    fq_half(y, tid & 63, ok, (uint32_t *)(P.qs[l] + (size_t)blk * 16), P.d[l] + blk);
-  }
-}
-
-// The LayerNorm of k_fast_ln in a GEMV workgroup's prologue: the residual row and the
-// affine are loaded (PER float4 of each per thread) before the workgroup's first weight
-// batch, the moments reduced while that batch is in flight, and the normalized row
-// quantized straight into the LDS activation slots (8 lanes per 32-value block, fq_oct).
+// (var = E[x^2] - mean^2 in double: one block reduction).  It runs in a GEMV workgroup's
+// prologue: the residual row and the affine are loaded (PER float4 of each per thread)
+// before the workgroup's first weight batch, the moments reduced while that batch is in
+// flight, and the normalized row quantized straight into the LDS activation slots (8 lanes
+// per 32-value block, fq_oct).
 template <int NT, int PER>
 struct LnStage {
   f32x4 x[PER], w[PER], b[PER];
@@ -608,16 +549,6 @@ __global__ void __launch_bounds__(64 * FD_OWAVES) k_fast_oproj_join(FastOproj P)
 }
 
 // ------------------------------------------------------------------ launchers
-int launch_fast_ln(const FastLn &P, hipStream_t s) {
-  if (P.E > FD_MAXE || P.E % (4 * QK) != 0 || P.n < 1 || P.n > 2) {
-    set_error("fast decode: n_embd must be a multiple of 128, at most 8192");
-    return VSIM_EINVAL;
-  }
-  hipLaunchKernelGGL(k_fast_ln, dim3(P.n * LN_SPLIT), dim3(LN_NT), 0, s, P);
-  VSIM_HIP(hipGetLastError());
-  return VSIM_OK;
-}
-
 int launch_fast_gemv(const FastGemv &P, int E, hipStream_t s) {
   int tiles = 0;
   for (int i = 0; i < P.nj; ++i) {

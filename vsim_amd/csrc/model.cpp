@@ -250,7 +250,7 @@ struct ScratchBuf {
 
 std::vector<ScratchBuf> scratch_table(vsim_model *m, size_t n) {
   const size_t E = E_(m), F = 4 * E, V = m->hp.n_vocab, H = m->hp.n_head, f = sizeof(float);
-  const size_t d = E / H, nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
+  const size_t d = E / H, nch = fast_nchunk(m->n_ctx);
   // counters of the fused layer kernels at [0], [64], [128] (separate 256-byte lines)
   // (k_layer_exact: one set per layer, [il - l0][256], zeroed by a memset node per token)
   const size_t ncnt = (size_t)std::max(1, m->l1 - m->l0) * 256;
@@ -725,16 +725,16 @@ struct PromptBatch {
     P.fused = pl.fused;
     if (pl.error) { set_error(pl.error); return VSIM_EINVAL; }
     // Weight-only mode never quantizes: the rows' fp16 operand (launch_w4a16_rows) takes the place
-    // of the Q4 rows' factors in P.xd ([N][K] halves in room for [N][K] floats), its exponents the
-    // place of the nibbles in P.xq, made and shared under the same `quantize` flag
+    // of the Q4 rows in P.xq / P.xd (w4a16_operand), made and shared under the same `quantize` flag
+    const W4a16Operand o = w4a16_operand({{P.xq}, P.xd});
     if (P.quantize && pl.w4a16) {
-      LAUNCH(m, nk, launch_w4a16_rows(P.x, K, N, P.xd, (int32_t *)P.xq, s), "k_w4a16_rows", (double)N * K * 6);
+      LAUNCH(m, nk, launch_w4a16_rows(P.x, K, N, o.h, o.e, s), "k_w4a16_rows", (double)N * K * 6);
     } else if (P.quantize && !P.x16) {
       RC(launch_q4_quantize(P.x, K, N, P.xq, P.xd, s));
       ++nk;
     }
     const long ev = prof_begin(m);
-    if (pl.w4a16) RC(launch_gemm_w4a16_rows(P.w, P.xd, (const int32_t *)P.xq, N, P.bias, P.y, s));
+    if (pl.w4a16) RC(launch_gemm_w4a16_rows(P.w, o.h, o.e, N, P.bias, P.y, s));
     switch (pl.kernel) {
       case ProductKernel::GEMM_F16_256:
         RC(launch_gemm_q4_256(P.w, P.x16, N, pl.gelu ? P.gq_bias : P.bias, P.y, s, pl.gelu ? P.gq : nullptr,
@@ -902,17 +902,10 @@ int run_layer(PromptBatch &B, int il) {
 // the same replayable form as enqueue_decode (token and n_past from device memory).
 // Shapes the fast step handles: head dim a multiple of 32 up to 256, rotary pairs inside one
 // 32-row tile (GPT-J pairs; GPT-NeoX rotate-half with n_rot <= 32), n_embd <= 8192.
-// fc_out K splits: FD_SF, doubled until one split's activation slice fits the LDS staging
-// (at most FD_MAXE values)
-int fast_sf(const vsim_model *m) {
-  int sf = FD_SF;
-  while (sf < 8 && 4 * m->hp.n_embd / sf > FD_MAXE) sf *= 2;
-  return sf;
-}
-
+// The launches' arguments come from decode_jobs.hpp (fast_gemv, fast_tail_job, fast_oproj_job).
 bool fast_decode_ok(const vsim_model *m) {
   const int E = m->hp.n_embd, H = m->hp.n_head, d = E / H;
-  const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
+  const int nch = fast_nchunk(m->n_ctx);
   return d % 32 == 0 && d <= 256 && E <= 8192 && E % 128 == 0 &&
          m->gd.residual == RES_PARALLEL && (m->gd.rotary == ROT_GPTJ || m->hp.n_rot <= 32) && 2 * H * nch <= 4096 &&
          nch <= FD_MAXCH;  // (launch_fast_tail's limit: a longer context takes the exact step)
@@ -924,14 +917,14 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
-  uint8_t *q1 = m->xq1, *q3 = m->xq3;
-  float *d1 = q4_rows(q1, E).d, *d2 = q4_rows(m->xq2, E).d, *d3 = q4_rows(q3, F).d;
+  // the Q4 rows of the step: fc_in's GELU output, the attention output (the norms' stay in LDS)
+  const Q4Rows x3 = q4_rows(m->xq3, F), xa = q4_rows(m->xqa, E);
   if (m->first) {
     RC(launch_get_rows(m->wte, E, V, m->tok_dev, 1, m->inpL, s));
     ++nk;
   }
-  const float scale = default_attn_scale(E, H);
-  const int nchunk = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
+  const int sf = fast_sf(E);
+  const FastPos pos{m->npast_dev, m->rope_cs, d, m->hp.n_rot, G.rotary == ROT_GPTJ ? 1 : 0};
   const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
   float *R[2] = {m->inpL, m->inpL2};
   int cur = 0;
@@ -940,77 +933,34 @@ int enqueue_decode_fast(vsim_model *m, int &nk) {
     const size_t loff = (size_t)(il - m->l0) * m->n_ctx * E;
     // LayerNorm(s) -> Q4 activations in the GEMV's prologue (GPT-J: one LayerNorm feeds
     // attention and MLP), then {fc_in -> GELU -> quantize, Q, K, V}
-    FastGemv P{};
-    P.lnx = R[cur];
-    P.lnw[0] = L.ln1_w;
-    P.lnb[0] = L.ln1_b;
-    P.lnw[1] = G.two_norms ? L.ln2_w : L.ln1_w;
-    P.lnb[1] = G.two_norms ? L.ln2_b : L.ln1_b;
-    P.xq[0] = q1;
-    P.xd[0] = d1;
-    P.xq[1] = G.two_norms ? m->xq2 : q1;
-    P.xd[1] = G.two_norms ? d2 : d1;
-    P.nj = 4;
-    P.j[0] = FastJob{w4_view(L.wfc, F, E), L.bfc, nullptr, FE_GELU_Q, 1};
-    P.j[1] = FastJob{w4_view(L.wq, E, E), G.qkvo_bias ? L.bq : nullptr, m->Qb, FE_ROPE_Q, 0};
-    P.j[2] = FastJob{w4_view(L.wk, E, E), G.qkvo_bias ? L.bk : nullptr, m->kcache + loff, FE_ROPE_K, 0};
-    P.j[3] = FastJob{w4_view(L.wv, E, E), G.qkvo_bias ? L.bv : nullptr, m->vcache + loff, FE_V, 0};
-    P.gelu_tab = tab.gelu_f16;
-    P.clear = m->tail_done;  // K2's per-head counters (tail_done[4h])
-    P.nclear = 4 * H;
-    P.oq_qs = q3;
-    P.oq_d = d3;
-    P.npast = m->npast_dev;
-    P.cs = m->rope_cs;
-    P.d = d;
-    P.n_rot = m->hp.n_rot;
-    P.style = G.rotary == ROT_GPTJ ? 1 : 0;
+    const float *bq = G.qkvo_bias ? L.bq : nullptr, *bk = G.qkvo_bias ? L.bk : nullptr,
+                *bv = G.qkvo_bias ? L.bv : nullptr, *bo = G.qkvo_bias ? L.bo : nullptr;
+    float *kc = m->kcache + loff, *vc = m->vcache + loff;
+    const NormRow n1{L.ln1_w, L.ln1_b}, n2{L.ln2_w, L.ln2_b};
+    const FastJob jobs[4] = {fast_job(L.wfc, F, E, L.bfc, nullptr, FE_GELU_Q, 1),
+                             fast_job(L.wq, E, E, bq, m->Qb, FE_ROPE_Q, 0), fast_job(L.wk, E, E, bk, kc, FE_ROPE_K, 0),
+                             fast_job(L.wv, E, E, bv, vc, FE_V, 0)};
+    const FastAct act{.lnx = R[cur], .n = {n1, G.two_norms ? n2 : n1}};
+    // (clears K2's per-head counters, tail_done[4h])
+    const FastGemv P = fast_gemv(act, jobs, 4, tab.gelu_f16, x3, pos, m->tail_done, 4 * H);
     LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (fc_in, Q, K, V)",
            w4_algo_bytes(P.j[0].w) + 3 * w4_algo_bytes(P.j[1].w));
-    // fc_out split over K | attention chunks
-    FastTail T{};
-    T.wf = w4_view(L.wproj, E, F);
-    T.xf_qs = q3;
-    T.xf_d = d3;
-    T.ffp = m->fast_ffp;
-    T.sf = fast_sf(m);
-    T.q = m->Qb;
-    T.kc = m->kcache + loff;
-    T.vc = m->vcache + loff;
-    T.npast = m->npast_dev;
-    T.d = d;
-    T.H = H;
-    T.nchunk = nchunk;
-    T.scale = scale;
-    T.part = m->fast_part;
-    T.hcnt = m->tail_done;
-    T.oq_qs = m->xqa;
-    T.oq_d = q4_rows(m->xqa, E).d;
-    // attention merge + out-projection + residual join into the other buffer
-    FastOproj O{};
-    O.w = w4_view(L.wo, E, E);
-    O.xq = T.oq_qs;
-    O.xd = T.oq_d;
-    O.d = d;
-    O.bo = G.qkvo_bias ? L.bo : nullptr;
-    O.ffp = m->fast_ffp;
-    O.sf = fast_sf(m);
-    O.bproj = L.bproj;
-    O.x = R[cur];
-    O.out = R[cur ^ 1];
+    // fc_out split over K | attention chunks, the last of a head merging them
+    const FastTail T = fast_tail_job(
+        w4_view(L.wproj, E, F), x3, m->fast_ffp, sf,
+        FastAttn{.q = m->Qb, .kc = kc, .vc = vc, .npast = m->npast_dev, .d = d, .H = H, .nchunk = fast_nchunk(m->n_ctx),
+                 .scale = default_attn_scale(E, H), .part = m->fast_part, .hcnt = m->tail_done, .o = xa});
     LAUNCH(m, nk, launch_fast_tail(T, s), "k_fast_tail (fc_out + attention)", w4_algo_bytes(T.wf) + kv_bytes);
+    // out-projection + residual join into the other buffer
+    const FastOproj O = fast_oproj_job(w4_view(L.wo, E, E), xa, bo, m->fast_ffp, sf, L.bproj, R[cur], R[cur ^ 1]);
     LAUNCH(m, nk, launch_fast_oproj_join(O, s), "k_fast_oproj_join", w4_algo_bytes(O.w));
     cur ^= 1;
   }
   if (m->last) {
-    FastGemv P{};
-    P.lnx = R[cur];
-    P.lnw[0] = P.lnw[1] = m->lnf_w;
-    P.lnb[0] = P.lnb[1] = m->lnf_b;
-    P.xq[0] = P.xq[1] = q1;
-    P.xd[0] = P.xd[1] = d1;
-    P.nj = 1;
-    P.j[0] = FastJob{w4_view(m->lmh, V, E), G.lmh_bias ? m->lmh_b : nullptr, m->logits, FE_STORE, 0};
+    const NormRow nf{m->lnf_w, m->lnf_b};
+    const FastJob head = fast_job(m->lmh, V, E, G.lmh_bias ? m->lmh_b : nullptr, m->logits, FE_STORE, 0);
+    const FastAct act{.lnx = R[cur], .n = {nf, nf}};
+    const FastGemv P = fast_gemv(act, &head, 1, nullptr, Q4Rows{}, FastPos{}, nullptr, 0);
     LAUNCH(m, nk, launch_fast_gemv(P, E, s), "k_fast_gemv (lm_head)", w4_algo_bytes(P.j[0].w));
   }
   m->resid_final = R[cur];
@@ -1262,34 +1212,23 @@ int enqueue_decode_w4a16(vsim_model *m, int &nk) {
   hipStream_t s = m->stream;
   DevTables tab;
   RC(tables_get(&tab));
-  // a row operand: halves where the exact step keeps a row's factors, the exponent where it keeps
-  // the nibbles (as the general path's products use the same buffers)
-  struct Operand {
-    _Float16 *h;
-    int32_t *e;
-  };
-  const Operand x1{(_Float16 *)m->xd1, (int32_t *)m->xq1}, x2{(_Float16 *)m->xd2, (int32_t *)m->xq2},
-      x3{(_Float16 *)m->xd3, (int32_t *)m->xq3}, xa{(_Float16 *)m->xda, (int32_t *)m->xqa};
+  // the row operands in the exact step's rows (as the general path's products use the same buffers);
+  // the attention's Q4 row goes where the f32 row's operand follows it
+  const ActRow ra{q4_rows(m->xqa, E), m->xda};
+  const W4a16Operand x1 = w4a16_operand({{m->xq1}, m->xd1}), x2 = w4a16_operand({{m->xq2}, m->xd2}),
+                     x3 = w4a16_operand({{m->xq3}, m->xd3}), xa = w4a16_operand(ra);
   const bool serial = G.residual != RES_PARALLEL, keep_joined = G.residual == RES_SERIAL_JOINED;
   const double kv_bytes = 2.0 * ((double)m->prof_npast + 1) * E * sizeof(float);
-  auto job = [&](const void *w, int M, int K, const Operand &x, const float *bias, float *y, const float *res = nullptr,
-                 const float *res_a = nullptr) {
-    return W4a16GemvJob{w4_view(w, M, K), x.h, x.e, bias, res, res_a, y};
-  };
-  auto ln = [&](const float *x, const float *w1, const float *b1, const Operand &o1, const float *w2, const float *b2,
-                const Operand &o2) {
-    const W4a16Ln A{x, E, w1, b1, o1.h, o1.e, w2, b2, w2 ? o2.h : nullptr, w2 ? o2.e : nullptr};
-    LAUNCH(m, nk, launch_w4a16_ln(A, s), "k_w4a16_ln", 4.0 * E * (w2 ? 5 : 3) + 2.0 * E * (w2 ? 2 : 1));
+  auto ln = [&](const float *x, const NormRow &n1, const W4a16Operand &o1, const NormRow *n2 = nullptr,
+                const W4a16Operand &o2 = {}) {
+    LAUNCH(m, nk, launch_w4a16_ln(w4a16_ln_job(x, E, n1, o1, n2, o2), s), "k_w4a16_ln",
+           4.0 * E * (n2 ? 5 : 3) + 2.0 * E * (n2 ? 2 : 1));
     return VSIM_OK;
   };
   auto gemv = [&](std::initializer_list<W4a16GemvJob> jobs, const char *what) {
-    W4a16Gemv B{};
     double bytes = 0.0;
-    for (const W4a16GemvJob &j : jobs) {
-      B.j[B.nj++] = j;
-      bytes += w4_algo_bytes(j.w);
-    }
-    LAUNCH(m, nk, launch_w4a16_gemv(B, s), std::string("k_gemv_w4a16 (") + what + ")", bytes);
+    for (const W4a16GemvJob &j : jobs) bytes += w4_algo_bytes(j.w);
+    LAUNCH(m, nk, launch_w4a16_gemv(w4a16_gemv(jobs), s), std::string("k_gemv_w4a16 (") + what + ")", bytes);
     return VSIM_OK;
   };
   for (int il = m->l0; il < m->l1; ++il) {
@@ -1298,35 +1237,36 @@ int enqueue_decode_w4a16(vsim_model *m, int &nk) {
     const float *bq = G.qkvo_bias ? L.bq : nullptr, *bk = G.qkvo_bias ? L.bk : nullptr,
                 *bv = G.qkvo_bias ? L.bv : nullptr, *bo = G.qkvo_bias ? L.bo : nullptr;
     const bool two_here = G.two_norms && !serial;  // both norms read the same row
-    RC(ln(m->inpL, L.ln1_w, L.ln1_b, x1, two_here ? L.ln2_w : nullptr, two_here ? L.ln2_b : nullptr, x2));
-    const W4a16GemvJob q = job(L.wq, E, E, x1, bq, m->Qb), k = job(L.wk, E, E, x1, bk, m->Kb),
-                       v = job(L.wv, E, E, x1, bv, m->Vb);
+    const NormRow n1{L.ln1_w, L.ln1_b}, n2{L.ln2_w, L.ln2_b};
+    RC(ln(m->inpL, n1, x1, two_here ? &n2 : nullptr, x2));
+    const W4a16GemvJob q = w4a16_gemv_job(L.wq, E, E, x1, bq, m->Qb), k = w4a16_gemv_job(L.wk, E, E, x1, bk, m->Kb),
+                       v = w4a16_gemv_job(L.wv, E, E, x1, bv, m->Vb);
     // fc_in's bias goes with the GELU
     if (serial)
       RC(gemv({q, k, v}, "Q, K, V"));
     else
-      RC(gemv({q, k, v, job(L.wfc, F, E, two_here ? x2 : x1, nullptr, m->fch)}, "Q, K, V, fc_in"));
-    // (the attention's Q4 row goes where the f32 row's operand follows it)
-    AttnJob A = attn_job(decode_attn_desc(m, tab, ActRow{q4_rows(m->xqa, E), m->xda}, 1), nullptr, nullptr, nullptr);
+      RC(gemv({q, k, v, w4a16_gemv_job(L.wfc, F, E, two_here ? x2 : x1, nullptr, m->fch)}, "Q, K, V, fc_in"));
+    AttnJob A = attn_job(decode_attn_desc(m, tab, ra, 1), nullptr, nullptr, nullptr);
     A.out = m->attn_in;
     const AttnRows R{m->w4_kv, m->w4_kv + 1, loff, m->npast_dev};
     LAUNCH(m, nk, launch_attn_decode_batch(A, R, 1, m->n_ctx, s), "k_attn_decode_batch", kv_bytes);
     LAUNCH(m, nk, launch_w4a16_rows(m->attn_in, E, 1, xa.h, xa.e, s), "k_w4a16_rows", (double)E * 6);
     if (serial) {
       // cur2 = attn + inpL, the MLP's input (BLOOM: and the residual)
-      RC(gemv({job(L.wo, E, E, xa, bo, m->cur2, m->inpL)}, "out-proj"));
-      RC(ln(m->cur2, L.ln2_w, L.ln2_b, x2, nullptr, nullptr, x2));
-      RC(gemv({job(L.wfc, F, E, x2, nullptr, m->fch)}, "fc_in"));
+      RC(gemv({w4a16_gemv_job(L.wo, E, E, xa, bo, m->cur2, m->inpL)}, "out-proj"));
+      RC(ln(m->cur2, n2, x2));
+      RC(gemv({w4a16_gemv_job(L.wfc, F, E, x2, nullptr, m->fch)}, "fc_in"));
     } else {
-      RC(gemv({job(L.wo, E, E, xa, bo, m->attn)}, "out-proj"));
+      RC(gemv({w4a16_gemv_job(L.wo, E, E, xa, bo, m->attn)}, "out-proj"));
     }
     LAUNCH(m, nk, launch_w4a16_gelu(m->fch, L.bfc, F, x3.h, x3.e, nullptr, s), "k_w4a16_gelu", (double)F * 10);
     // the layer's join in fc_out's epilogue (k_add_residual's orders; BLOOM: ff + the joined row)
-    RC(gemv({job(L.wproj, E, F, x3, L.bproj, m->inpL, keep_joined ? m->cur2 : m->inpL, serial ? nullptr : m->attn)},
+    RC(gemv({w4a16_gemv_job(L.wproj, E, F, x3, L.bproj, m->inpL, keep_joined ? m->cur2 : m->inpL,
+                            serial ? nullptr : m->attn)},
             "fc_out"));
   }
-  RC(ln(m->inpL, m->lnf_w, m->lnf_b, x1, nullptr, nullptr, x1));
-  RC(gemv({job(m->lmh, V, E, x1, G.lmh_bias ? m->lmh_b : nullptr, m->logits)}, "lm_head"));
+  RC(ln(m->inpL, NormRow{m->lnf_w, m->lnf_b}, x1));
+  RC(gemv({w4a16_gemv_job(m->lmh, V, E, x1, G.lmh_bias ? m->lmh_b : nullptr, m->logits)}, "lm_head"));
   m->resid_final = m->inpL;
   return VSIM_OK;
 }
@@ -1891,8 +1831,7 @@ int vsim_model_set_mode(vsim_model *m, int mode) {
   }
   // A context of more than FD_MAXCH chunks is beyond the fast decode step's merge
   // (launch_fast_tail refuses it): such a model runs in exact mode throughout
-  const int nch = (m->n_ctx + FD_CHUNK - 1) / FD_CHUNK;
-  m->mode = mode == VSIM_MODE_FAST && nch > FD_MAXCH ? VSIM_MODE_EXACT : mode;
+  m->mode = mode == VSIM_MODE_FAST && fast_nchunk(m->n_ctx) > FD_MAXCH ? VSIM_MODE_EXACT : mode;
   return VSIM_OK;
 }
 
