@@ -102,7 +102,11 @@ int vsim_ggml_mul_mat_f32(const struct ggml_compute_params *params, const struct
  * cgraph->n_threads, so the logits equal the reference's at any --threads.
  * vsim_graph_compute prints the error and exits (as the reference's offload layer does,
  * imax.c:2042-2049); vsim_graph_compute_rc returns VSIM_E* instead and leaves host memory
- * untouched when a node is not supported (all nodes are checked before any runs). */
+ * untouched when a node is not supported (all nodes are checked before any runs).
+ * The parameter tensors of scale (the factor), diag_mask_inf (n_past), rope and gptneox_rope
+ * ({n_past, n_dims, mode}) are read from host memory when the node is enqueued, so they must be
+ * leafs (op NONE): one that is itself a node of the graph is refused with VSIM_EINVAL
+ * ("parameter must be a leaf"), where the reference would read it at compute time. */
 void vsim_graph_compute(struct ggml_context *ctx, struct ggml_cgraph *cgraph);
 int vsim_graph_compute_rc(struct ggml_context *ctx, struct ggml_cgraph *cgraph);
 /* copy one tensor of the last computed graph back to its host address */

@@ -315,6 +315,8 @@ int node(const ggml_tensor *n, int nth, bool dry) {
     case GGML_OP_SCALE: {
       NEED(a && b && n->data == a->data && contiguous(n) && nelem(b) == 1 && b->type == GGML_TYPE_F32,
            "scale: in place on a contiguous tensor by an F32 scalar");
+      // the value is read from host memory here; a node's value exists only on the device
+      NEED(b->op == GGML_OP_NONE && b->data, "scale: parameter must be a leaf");
       char *dn = dev_of_t(n);
       NEED(dn, "scale: operand outside the mirrored memory");
       if (dry) return VSIM_OK;
@@ -323,6 +325,7 @@ int node(const ggml_tensor *n, int nth, bool dry) {
     case GGML_OP_DIAG_MASK_INF: {
       NEED(a && b && n->data == a->data && nelem(b) == 1 && b->type == GGML_TYPE_I32 && n->nb[0] == 4,
            "diag_mask_inf: in place, I32 n_past");
+      NEED(b->op == GGML_OP_NONE && b->data, "diag_mask_inf: parameter must be a leaf");
       char *dn = dev_of_t(n);
       NEED(dn, "diag_mask_inf: operand outside the mirrored memory");
       if (dry) return VSIM_OK;
@@ -343,6 +346,7 @@ int node(const ggml_tensor *n, int nth, bool dry) {
       NEED(a && b && n->data == a->data && contiguous(n) && n->type == GGML_TYPE_F32 && n->ne[3] == 1,
            "rope: in place on a contiguous [d, H, T] tensor");
       NEED(b->type == GGML_TYPE_I32 && nelem(b) == 3, "rope: parameters {n_past, n_dims, mode}");
+      NEED(b->op == GGML_OP_NONE && b->data, "rope: parameter must be a leaf");
       const int32_t *pr = (const int32_t *)b->data;
       const int n_past = pr[0], n_dims = pr[1], mode = pr[2];
       NEED(n_dims > 0 && n_dims % 2 == 0 && n_dims <= n->ne[0] && (mode == 0 || mode == 1), "rope: parameters");
