@@ -254,6 +254,23 @@ int vsim_op_q4_gemm_fast_rows(const void *w, int M, int K, const void *xq, int n
 int vsim_op_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, void *stream);
 int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, const int32_t *e, int n,
                                const float *bias, float *y, void *stream);
+/* vsim_op_q4_gemm_w4a16_tile (k_gemm_w4a16_tile): the same product for any n >= 1 in one launch, tiled
+ * over 64 (or 32) weight rows x 64 activation rows per workgroup, so that the weight streams once
+ * per 64 activation rows.  y [n][M] is bit for bit vsim_op_q4_gemm_w4a16_rows on consecutive chunks
+ * of 32 rows: the formula above per (weight row, activation row) pair -- the same MFMA from C = 0
+ * per block, the same sixteen fma strands, the same ordered sum -- with contracts (a) and (b), the
+ * NaN rule and the read and write limits unchanged.  It always runs the tile kernel
+ * (vsim_w4a16_set_tile_gemm does not apply to it).  VSIM_EINVAL as vsim_op_q4_gemm_w4a16_rows, without
+ * the upper limit on n. */
+int vsim_op_q4_gemm_w4a16_tile(const void *w, int M, int K, const void *x16, const int32_t *e, int n,
+                               const float *bias, float *y, void *stream);
+/* Process-wide choice of how the products of a weight-only prompt batch (vsim_model_eval at N > 1,
+ * _eval_seq, _eval_score) run: 0: k_gemm_w4a16_rows on chunks of 32 rows at every N (the weight
+ * streams once per chunk); 1 (default): k_gemm_w4a16_tile from the smallest N where it was measured
+ * faster by more than 5 % (profiles/w4a16_prompt_bench.txt), the chunks below; 2: k_gemm_w4a16_tile
+ * at every N.  All three give the same bits.  The batched step (vsim_model_decode_batch_w4a16) and
+ * the single-token step are not affected.  Other values select 1.  Returns the previous value. */
+int vsim_w4a16_set_tile_gemm(int v);
 /* ---- weight-only mode: the kernels of the single-token step (w4a16_decode.hip).  Each is, bit for
  * bit, a composition of entries above on the same row; none has a tolerance of its own.
  *
@@ -838,8 +855,9 @@ int vsim_model_randomize(vsim_model *m, uint64_t seed, float std);
  * model (layers [0, n_layer)) at any n_ctx; VSIM_EINVAL on a pipeline stage.  Every kernel of the
  * mode is per row, so in this mode, bit for bit:
  *   - an eval of N tokens leaves the cache rows of N single-token evals, and its logits row is
- *     theirs (a product of N rows is ceil(N / 32) launches of the rows kernel on consecutive
- *     32-row chunks: a chunked weight pass, chosen because chunking cannot change a row's bits);
+ *     theirs (a product of N rows is one launch of vsim_op_q4_gemm_w4a16_tile's kernel from 33 rows
+ *     on, and ceil(N / 32) launches of the rows kernel on consecutive 32-row chunks below or with
+ *     vsim_w4a16_set_tile_gemm(0): neither tiling nor chunking changes a row's bits);
  *   - row i of vsim_model_eval_score's logits_all is the logits row of the eval ending at i,
  *     whatever the head's chunk size;
  *   - row b of vsim_model_decode_batch_w4a16 is vsim_model_eval_seq's row for that sequence alone;

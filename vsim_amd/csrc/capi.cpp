@@ -187,6 +187,15 @@ int vsim_op_q4_gemm_w4a16_rows(const void *w, int M, int K, const void *x16, con
   }
   return launch_gemm_w4a16_rows(w4_view(w, M, K), x16, e, n, bias, y, (hipStream_t)stream);
 }
+int vsim_op_q4_gemm_w4a16_tile(const void *w, int M, int K, const void *x16, const int32_t *e, int n, const float *bias,
+                               float *y, void *stream) {
+  if (!w || !x16 || !e || !y || M <= 0 || K <= 0 || K % QK || n < 1) {
+    set_error("q4_gemm_w4a16_tile: at least one activation row, K a multiple of 32, M > 0, w, x16, e and y required");
+    return VSIM_EINVAL;
+  }
+  return launch_gemm_w4a16_tile(w4_view(w, M, K), x16, e, n, bias, y, (hipStream_t)stream);
+}
+int vsim_w4a16_set_tile_gemm(int v) { return w4a16_set_tile_gemm(v); }
 int vsim_op_w4a16_ln(const vsim_w4a16_ln_args *a, void *stream) {
   if (!a) { set_error("w4a16_ln: null argument"); return VSIM_EINVAL; }
   DevTables tab;  // (the device's LayerNorm counters come with its tables)

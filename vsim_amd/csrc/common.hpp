@@ -327,6 +327,10 @@ int launch_gemm_fast_rows(const W4 &W, const void *xq, int n, const float *bias,
 int launch_w4a16_rows(const float *x, int K, int n, void *x16, int32_t *e, hipStream_t s);
 int launch_gemm_w4a16_rows(const W4 &W, const void *x16, const int32_t *e, int n, const float *bias, float *y,
                            hipStream_t s);
+// The same product tiled over weight rows and activation rows, n of any size in one launch
+// (gemm_w4a16_tile.hip; vsim_op_q4_gemm_w4a16_tile): launch_gemm_w4a16_rows' bits and argument checks
+int launch_gemm_w4a16_tile(const W4 &W, const void *x16, const int32_t *e, int n, const float *bias, float *y,
+                           hipStream_t s);
 // Weight-only mode's single-token step (w4a16_decode.hip; vsim_op_w4a16_ln, _gelu, _gemv): each the
 // bits of the kernels above (and launch_norm, launch_gelu, launch_add_residual) on the same row.
 // LayerNorm of x[n] with (w1, b1) straight to the row operand (h1, e1), and optionally with (w2, b2)

@@ -721,7 +721,7 @@ struct PromptBatch {
     hipStream_t s = m->stream;
     const ProductPlan pl = product_plan({.kind = D.kind, .mode = D.mode, .N = N, .M = M, .K = K, .x16 = P.x16 != nullptr,
                                          .gelu = P.gq && P.gq_bias, .epi = P.epi != nullptr, .gemm = batch_gemm(),
-                                         .fast_gemm = batch_fast_gemm()});
+                                         .fast_gemm = batch_fast_gemm(), .w4a16_tile = w4a16_tile_gemm()});
     P.fused = pl.fused;
     if (pl.error) { set_error(pl.error); return VSIM_EINVAL; }
     // Weight-only mode never quantizes: the rows' fp16 operand (launch_w4a16_rows) takes the place
@@ -734,7 +734,8 @@ struct PromptBatch {
       ++nk;
     }
     const long ev = prof_begin(m);
-    if (pl.w4a16) RC(launch_gemm_w4a16_rows(P.w, o.h, o.e, N, P.bias, P.y, s));
+    if (pl.w4a16_tile) RC(launch_gemm_w4a16_tile(P.w, o.h, o.e, N, P.bias, P.y, s));
+    else if (pl.w4a16) RC(launch_gemm_w4a16_rows(P.w, o.h, o.e, N, P.bias, P.y, s));
     switch (pl.kernel) {
       case ProductKernel::GEMM_F16_256:
         RC(launch_gemm_q4_256(P.w, P.x16, N, pl.gelu ? P.gq_bias : P.bias, P.y, s, pl.gelu ? P.gq : nullptr,

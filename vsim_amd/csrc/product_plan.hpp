@@ -44,15 +44,27 @@ constexpr int BATCH_GEMM_MIN_N = 12;
 // shapes (profiles/batch_fast_bench.txt: GPT-J-6B 1.07x at B = 2, 1.58x at 4;
 // batch_fast_bench_pythia12b.txt: 0.78x at B = 2, 1.18x at 4)
 constexpr int BATCH_FAST_GEMM_MIN_N = 4;
+// from this many rows on the products of a weight-only prompt batch run on k_gemm_w4a16_tile by
+// default, in one launch, instead of k_gemm_w4a16_rows on chunks of VSIM_BATCH_MAX rows: the smallest
+// measured N of {33, 64, 96, 128, 256} at which a prompt eval on it beats the chunked one by more
+// than 5 % at both measured shapes (profiles/w4a16_prompt_bench.txt: GPT-J-6B 1.07x at N = 33, 1.14x
+// at 64, 1.49x at 96, 1.77x at 128, 2.35x at 256; pythia-12b 1.48x, 1.59x, 1.76x, 1.84x, 2.52x)
+constexpr int W4A16_TILE_MIN_N = 33;
+// ... and the activation rows of one of its workgroups: the weight streams once per this many rows
+constexpr int W4A16_TILE_ROWS = 64;
 
 // The process-wide switches (0: the GEMV path, 1: the rows GEMM from its threshold on, 2: always;
-// another value selects 1).  The setters return the old setting.
+// another value selects 1; the weight-only prompt's: 0: the chunked rows kernel, 1: the tile kernel
+// from its threshold on, 2: always).  The setters return the old setting.
 inline std::atomic<int> g_batch_gemm{1};       // vsim_batch_set_gemm
 inline std::atomic<int> g_batch_fast_gemm{1};  // vsim_batch_set_fast_gemm
+inline std::atomic<int> g_w4a16_tile_gemm{1};  // vsim_w4a16_set_tile_gemm
 inline int batch_set_gemm(int v) { return g_batch_gemm.exchange(v < 0 || v > 2 ? 1 : v); }
 inline int batch_set_fast_gemm(int v) { return g_batch_fast_gemm.exchange(v < 0 || v > 2 ? 1 : v); }
+inline int w4a16_set_tile_gemm(int v) { return g_w4a16_tile_gemm.exchange(v < 0 || v > 2 ? 1 : v); }
 inline int batch_gemm() { return g_batch_gemm.load(); }
 inline int batch_fast_gemm() { return g_batch_fast_gemm.load(); }
+inline int w4a16_tile_gemm() { return g_w4a16_tile_gemm.load(); }
 
 // The two row-count thresholds of the fp16 GEMMs, each compared here and nowhere else:
 // fast-mode rows that go to the fp16 GEMM, and an fp16 operand that goes to its 256-wide tiles
@@ -81,6 +93,7 @@ struct ProductQuery {
   bool gelu = false;  // asked for: bias + GELU + quantize of the product into the next fp16 operand
   bool epi = false;   // asked for: a G2Epi epilogue (RoPE, residual join, fp16 copies)
   int gemm = 1, fast_gemm = 1;  // the switches' settings (batch_gemm(), batch_fast_gemm())
+  int w4a16_tile = 1;           // ... and w4a16_tile_gemm()
 };
 
 struct ProductPlan {
@@ -95,6 +108,8 @@ struct ProductPlan {
   // operand, one launch per chunk of VSIM_BATCH_MAX rows; `kernel` stays NONE
   bool w4a16 = false;
   const char *error = nullptr;
+  // ... or, with w4a16 set too, k_gemm_w4a16_tile (launch_gemm_w4a16_tile) in one launch: the same bits
+  bool w4a16_tile = false;
 };
 
 // kernels_per_eval is not consistent about launches: a product on the GEMV paths of the general
@@ -111,11 +126,17 @@ inline ProductPlan product_plan(const ProductQuery &q) {
     p.name = name;
   };
   if (q.mode == VSIM_MODE_W4A16 || q.kind == BatchKind::ROWS_W4A16) {
-    // weight-only mode: the per-row kernel on consecutive chunks of VSIM_BATCH_MAX rows at every N
-    // (a chunked weight pass for a long prompt: chunking cannot change a row's bits)
+    // weight-only mode: the per-row kernel on consecutive chunks of VSIM_BATCH_MAX rows (a chunked
+    // weight pass: chunking cannot change a row's bits), or for a prompt batch, by the switch, the
+    // tile kernel that gives every row the same bits in one launch
     const int chunks = (q.N + VSIM_BATCH_MAX - 1) / VSIM_BATCH_MAX;
+    const bool prompt = q.kind == BatchKind::PROMPT || q.kind == BatchKind::PROMPT_SLOT;
     if (q.x16 || q.gelu || q.epi || q.mode != VSIM_MODE_W4A16) {
       p.error = "weight-only mode: a product left the f32 rows";
+    } else if (prompt && (q.w4a16_tile == 2 || (q.w4a16_tile == 1 && q.N >= W4A16_TILE_MIN_N))) {
+      is(PK::NONE, 1, 1, "k_gemm_w4a16_tile");
+      p.w4a16 = p.w4a16_tile = true;
+      p.passes = (q.N + W4A16_TILE_ROWS - 1) / W4A16_TILE_ROWS;
     } else {
       is(PK::NONE, chunks, chunks, "k_gemm_w4a16_rows");
       p.w4a16 = true;

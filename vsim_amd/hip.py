@@ -62,9 +62,11 @@ EXPORTS = [
     "vsim_model_decode_batch_sample_w4a16",
     "vsim_op_ln_quant", "vsim_op_gemv_batch",
     "vsim_op_w4a16_ln", "vsim_op_w4a16_gelu", "vsim_op_w4a16_gemv", "vsim_w4a16_set_step",
+    "vsim_op_q4_gemm_w4a16_tile", "vsim_w4a16_set_tile_gemm",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
+W4A16_TILE_MIN_N = 33  # product_plan.hpp: a weight-only prompt of this many rows runs k_gemm_w4a16_tile
 
 SRC_F32, SRC_F16 = 0, 1  # VSIM_SRC_*
 LOAD_QUANTIZE = 1        # VSIM_LOAD_QUANTIZE
@@ -369,6 +371,8 @@ def lib():
     L.vsim_op_w4a16_gelu.argtypes = [vp, vp, ci, vp, vp, vp, vp]
     L.vsim_op_w4a16_gemv.argtypes = [ctypes.POINTER(W4a16GemvArgs), vp]
     L.vsim_w4a16_set_step.argtypes = [ci]
+    L.vsim_op_q4_gemm_w4a16_tile.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
+    L.vsim_w4a16_set_tile_gemm.argtypes = [ci]
     L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
     _lib = L
     return L
@@ -541,6 +545,22 @@ def q4_gemm_w4a16_rows(w, M, K, x16, e, n, bias, y, stream=None):
     not synchronized."""
     check(lib().vsim_op_q4_gemm_w4a16_rows(ptr(w), M, K, ptr(x16), ptr(e), n, ptr(bias), ptr(y), stream),
           "q4_gemm_w4a16_rows")
+
+
+def q4_gemm_w4a16_tile(w, M, K, x16, e, n, bias, y, stream=None):
+    """vsim_op_q4_gemm_w4a16_tile on device buffers (torch tensors): y [n][M] = the W4T32 weight w
+    [M][K] times the n >= 1 rows of w4a16_rows' operand (x16, e) in one launch of the tile kernel; bit
+    for bit q4_gemm_w4a16_rows on consecutive chunks of BATCH_MAX rows.  Enqueued on `stream`, not
+    synchronized."""
+    check(lib().vsim_op_q4_gemm_w4a16_tile(ptr(w), M, K, ptr(x16), ptr(e), n, ptr(bias), ptr(y), stream),
+          "q4_gemm_w4a16_tile")
+
+
+def w4a16_set_tile_gemm(v) -> int:
+    """vsim_w4a16_set_tile_gemm: how a weight-only prompt batch's products run (0: the rows kernel on
+    chunks of BATCH_MAX rows, 1: the tile kernel from its threshold on, 2: the tile kernel at every N;
+    the same bits).  Returns the previous value."""
+    return int(lib().vsim_w4a16_set_tile_gemm(int(v)))
 
 
 def w4a16_ln(x, n, w1, b1, x16_1, e1, w2=None, b2=None, x16_2=None, e2=None, stream=None):
