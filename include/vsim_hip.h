@@ -700,6 +700,66 @@ int vsim_gemm_set_tile_order(int cols);
  * straight to the next GEMM's fp16 operand: quantize_row_q4_0 per 32-value block, d*(q-8) as
  * fp16 -- what vsim_op_act_quant_f16 makes of the normalized rows. */
 int vsim_op_norm_f16q(const float *x, int k, int rows, const float *w, const float *b, void *x16, void *stream);
+/* ---- the fast-mode prompt layer, launch by launch (run_layer / PromptBatch::mm / run_head in
+ * VSIM_MODE_FAST): with the entries above, these make every launch of a prompt eval callable on
+ * caller buffers, with the model's arguments.  Which launch the model takes follows from values
+ * alone (N rows at n_past, E = n_embd, H heads of d = E / H dims, F = 4 E):
+ *   N < 8     the rows stay f32 / Q4: vsim_op_norm, vsim_op_q4_quantize once per distinct activation
+ *             (the norm's rows serve Q, K, V -- and fc_in of a one-norm graph), vsim_op_q4_gemv in
+ *             VSIM_MODE_FAST, vsim_op_gelu_bias in place, and the attention as vsim_op_kq_causal,
+ *             vsim_op_attn_softmax (vsim_op_attn_softmax_alibi for BLOOM), vsim_op_kqv_causal_merged.
+ *   N >= 8    every activation is the GEMMs' fp16 operand: vsim_op_norm_f16q, vsim_op_act_quant_f16
+ *             (the attention's output; fc_in's with bias and GELU), and the products on
+ *             vsim_op_gemm_q4_f16x -- or, from N >= 256 with E % 64 == 0, on vsim_op_gemm_q4_256,
+ *             where fc_in takes the GELU-quantize epilogue (q16), fc_out the residual join (join = 1
+ *             with res_a = the out-projection's rows for a parallel residual, NULL for GPT-NeoX's
+ *             serial one; BLOOM's fc_out stays plain), and a GPT-J layer's Q and K the RoPE epilogue
+ *             with p0 = n_past, K and V written straight to their cache rows.  Q and K of such a
+ *             layer are one vsim_op_gemm_q4_256_pair* launch when E % 256 == 0 (unless
+ *             vsim_gemm_set_qk_pair(0)), else two launches.
+ *             The attention is vsim_op_attn_prefill_scratch on the model's own scratch when d is one
+ *             of 64, 96, 128, 256 and E % 64 == 0 and the graph has no ALiBi (else the three exact
+ *             kernels as for N < 8); with the RoPE epilogue the K and V launches are the _h16 forms
+ *             (K16 rows at the scratch's start, V^T at vt_off with h16_ld = ldt, both of
+ *             vsim_op_attn_prefill_layout(E, n_past + N)) and fresh = 1; d = 256 writes out16 = the
+ *             out-projection's operand and no vsim_op_act_quant_f16 follows.
+ *   Without the RoPE epilogue Q, K, V land in row buffers and vsim_op_rope_kv_write moves them.
+ *   The joins outside an epilogue: vsim_op_add_residual; a two-norm serial graph first copies the
+ *   out-projection's rows and adds the residual to the copy (vsim_op_add_rows: attn + inpL), which
+ *   its second norm reads; BLOOM ends a layer with a copy of that joined row and vsim_op_add_rows of
+ *   fc_out's rows (inpFF + ff).
+ *   The last row's head of an eval is the N = 1 case: vsim_op_norm, vsim_op_q4_quantize,
+ *   vsim_op_q4_gemv; vsim_model_eval_score's chunks of C rows take the N = C rule.
+ *
+ * vsim_op_gemm_q4_f16x: y[n][M] (+ bias[M]) = the W4T32 weight w [M][K] times the fp16 operand x16
+ * [n][K] on the small-tile fp16 MFMA GEMM (k_gemm_q4_f16; K % 32 == 0): vsim_op_q4_gemv's
+ * VSIM_MODE_FAST product at n >= 8 without its conversion of Q4 rows, the weight's values d*(q-8)
+ * rounded once to fp16, fp32 accumulation. */
+int vsim_op_gemm_q4_f16x(const void *w, int M, int K, const void *x16, int n, const float *bias, float *y,
+                         void *stream);
+/* The prompt's RoPE + KV-cache write (vsim.cpp:553-580) in one launch: Q [N][H d] rotated in place
+ * at positions n_past + i; K rotated into kcache rows n_past + i, V copied into vcache rows n_past +
+ * i (kcache, vcache: one layer's [n_ctx][H d]).  style as vsim_op_rope; only the first n_rot dims of
+ * a head rotate (n_rot = 0: none, BLOOM); the double products are rounded once to float.  The
+ * cos / sin table is the library's own, as the model builds it; the call waits for the stream. */
+int vsim_op_rope_kv_write(int style, float *Q, const float *K, const float *V, float *kcache, float *vcache, int d,
+                          int H, int N, int n_past, int n_rot, void *stream);
+/* The residual join of n values: inpL = inpL + (attn + ff) (vsim.cpp:694-695), or with
+ * order_ff_first != 0 inpL = ff + inpL (vsim.cpp:657; attn unused, may be NULL).  And x += b over n
+ * values, the elementwise use of the bias add (vsim.cpp:629: cur + inpL). */
+int vsim_op_add_residual(float *inpL, const float *attn, const float *ff, int n, int order_ff_first, void *stream);
+int vsim_op_add_rows(float *x, const float *b, int n, void *stream);
+/* vsim_op_gelu of x[i] + bias[i % bias_len] (ggml_add, then ggml_gelu: vsim.cpp:680-683) */
+int vsim_op_gelu_bias(const float *x, float *y, int n, const float *bias, int bias_len, void *stream);
+/* vsim_op_attn_softmax with ggml_alibi between the scale and the mask (BLOOM): row j of head z gets
+ * (j + 1) * alibi[z] added (device slopes, [nz]).  vsim_op_alibi_slopes: the slopes as the model
+ * computes them, into a host array of n_head floats. */
+int vsim_op_attn_softmax_alibi(float *p, int nc, int nr, int nz, int n_past, float scale, const float *alibi,
+                               void *stream);
+int vsim_op_alibi_slopes(float *slopes_host, int n_head);
+/* vsim_op_kqv_causal with the heads merged as the model stores them: out[q][h d + c]. */
+int vsim_op_kqv_causal_merged(const float *V, int ldv, const float *S, int d, int H, int nk, int n, int n_past,
+                              float *out, void *stream);
 /* ---- fast-mode decode step, kernel by kernel (fast_decode.hip; the launches of the model's
  * fast step with the same parameter blocks).  Q4 SoA rows are vsim_op_q4_quantize's xq for n = 1:
  * the nibble plane [k/32][16], then the k/32 float scales.

@@ -36,6 +36,27 @@ def q4_f16_ref(y):
     return (d[:, None].astype(np.float64) * q).astype(np.float16).reshape(np.shape(y))
 
 
+def w16_of(w_aos, K):
+    """The fp16 weight operand of the prompt GEMMs: each Q4_0 value d*(q-8) rounded ONCE to
+    fp16 from its exact value (gemm_f16.hip deq_word_f16: one v_fma_mix; the product d*(q-8)
+    is exact in fp64 and numpy's fp64 -> fp16 conversion rounds to nearest even directly)."""
+    blk = np.asarray(w_aos, dtype=np.uint8).reshape(-1, 20)
+    d = blk[:, :4].copy().view(np.float32).reshape(-1).astype(np.float64)
+    q = np.empty((blk.shape[0], 32), dtype=np.float64)
+    q[:, 0::2] = (blk[:, 4:] & 0xF).astype(np.float64) - 8
+    q[:, 1::2] = (blk[:, 4:] >> 4).astype(np.float64) - 8
+    return (q * d[:, None]).astype(np.float16).reshape(-1, K)
+
+
+def gemm_f16_tol(K, abs16, bias=None):
+    """The fp16 MFMA GEMMs' per-element bound against the fp64 product of the fp16-rounded operands
+    (tests/test_gpu_ops.py test_prefill_gemm_f16): products of two fp16 are exact in fp32, the fp32
+    accumulation of K of them in any order stays within 4 K 2^-24 sum |w16 x16| (abs16), and the
+    bias add within 1e-6 |b|."""
+    t = 4.0 * K * 2.0 ** -24 * np.asarray(abs16, np.float64)
+    return t if bias is None else t + 1e-6 * np.abs(np.asarray(bias, np.float64))
+
+
 def q4_parse(aos, k):
     """ggml AoS blocks (fp32 d + 16 nibble bytes: lo = element 2l, hi = 2l+1) of rows of k values ->
     d [rows][nb] float32, q [rows][nb][32] signed."""

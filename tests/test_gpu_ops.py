@@ -9,7 +9,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from fast_ref import q4_f16_ref as _q4_f16_ref  # noqa: E402
+from fast_ref import gemm_f16_tol, q4_f16_ref as _q4_f16_ref, w16_of  # noqa: E402,F401
 from golden_util import cases, ops  # noqa: E402
 from vsim_amd import hip  # noqa: E402
 from vsim_amd import modelgen as mg  # noqa: E402
@@ -407,17 +407,6 @@ def test_gemv_exact_full_width_vs_oracle(M, K):
 
 
 
-def w16_of(w_aos, K):
-    """The fp16 weight operand of the prompt GEMMs: each Q4_0 value d*(q-8) rounded ONCE to
-    fp16 from its exact value (gemm_f16.hip deq_word_f16: one v_fma_mix; the product d*(q-8)
-    is exact in fp64 and numpy's fp64 -> fp16 conversion rounds to nearest even directly)."""
-    blk = np.asarray(w_aos, dtype=np.uint8).reshape(-1, mg.QBYTES)
-    d = blk[:, :4].copy().view(np.float32).reshape(-1).astype(np.float64)
-    q = np.empty((blk.shape[0], 32), dtype=np.float64)
-    q[:, 0::2] = (blk[:, 4:] & 0xF).astype(np.float64) - 8
-    q[:, 1::2] = (blk[:, 4:] >> 4).astype(np.float64) - 8
-    return (q * d[:, None]).astype(np.float16).reshape(-1, K)
-
 @pytest.mark.parametrize("M,K,N", [(520, 512, 300), (256, 4096, 8), (1000, 1024, 129), (96, 96, 40)])
 def test_prefill_gemm_f16(M, K, N):
     """Fast-mode prompt GEMM (gemm_f16.hip: fp16 MFMA after in-LDS dequant).  Operands are
@@ -440,7 +429,7 @@ def test_prefill_gemm_f16(M, K, N):
     X16 = X.astype(np.float16).astype(np.float64)
     ref16 = X16 @ W16.T + b
     abs16 = np.abs(X16) @ np.abs(W16).T
-    assert np.all(np.abs(y - ref16) <= 4.0 * K * 2.0 ** -24 * abs16 + 1e-6 * np.abs(b))
+    assert np.all(np.abs(y - ref16) <= gemm_f16_tol(K, abs16, b))
     ref = X.astype(np.float64) @ W.astype(np.float64).T + b
     absum = np.abs(X.astype(np.float64)) @ np.abs(W.astype(np.float64)).T
     assert np.all(np.abs(y - ref) <= 2.0 ** -10 * absum + 1e-5 * (np.abs(b) + 1))

@@ -710,6 +710,52 @@ int vsim_op_gemm_q4_256_pair_h16(const void *w0, const void *w1, int M, int K, c
 int vsim_op_norm_f16q(const float *x, int k, int rows, const float *w, const float *b, void *x16, void *stream) {
   return launch_norm_f16q(x, x16, k, rows, w, b, (hipStream_t)stream);
 }
+// ---- the launches of the fast-mode prompt layer (run_layer) that had no entry of their own
+int vsim_op_gemm_q4_f16x(const void *w, int M, int K, const void *x16, int n, const float *bias, float *y,
+                         void *stream) {
+  if (!w || !x16 || !y || M <= 0 || K <= 0 || K % QK || n <= 0) { set_error("gemm_q4_f16x: bad argument"); return VSIM_EINVAL; }
+  return launch_gemm_f16x(w4_view(w, M, K), x16, n, bias, y, (hipStream_t)stream);
+}
+int vsim_op_rope_kv_write(int style, float *Q, const float *K, const float *V, float *kcache, float *vcache, int d,
+                          int H, int N, int n_past, int n_rot, void *stream) {
+  if (!Q || !K || !V || !kcache || !vcache || d <= 0 || H <= 0 || N <= 0 || n_past < 0 || (style != 0 && style != 1) ||
+      n_rot < 0 || n_rot % 2 || n_rot > d) {
+    set_error("rope_kv_write: bad argument");
+    return VSIM_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (n_rot == 0) return launch_rope_kv_write(style, Q, K, V, kcache, vcache, d, H, N, n_past, 0, nullptr, s);
+  return with_rope_table(n_past + N, n_rot, s, [&](const double2 *cs) {
+    return launch_rope_kv_write(style, Q, K, V, kcache, vcache, d, H, N, n_past, n_rot, cs, s);
+  });
+}
+int vsim_op_add_residual(float *inpL, const float *attn, const float *ff, int n, int order_ff_first, void *stream) {
+  if (!inpL || !ff || (!order_ff_first && !attn) || n <= 0) { set_error("add_residual: bad argument"); return VSIM_EINVAL; }
+  return launch_add_residual(inpL, attn, ff, n, order_ff_first ? 1 : 0, (hipStream_t)stream);
+}
+int vsim_op_add_rows(float *x, const float *b, int n, void *stream) {
+  if (!x || !b || n <= 0) { set_error("add_rows: bad argument"); return VSIM_EINVAL; }
+  return launch_add_bias(x, b, n, 1, (hipStream_t)stream);
+}
+int vsim_op_gelu_bias(const float *x, float *y, int n, const float *bias, int bias_len, void *stream) {
+  if (!x || !y || !bias || n <= 0 || bias_len <= 0) { set_error("gelu_bias: bad argument"); return VSIM_EINVAL; }
+  return launch_gelu(x, y, n, bias, bias_len, (hipStream_t)stream);
+}
+int vsim_op_attn_softmax_alibi(float *p, int nc, int nr, int nz, int n_past, float scale, const float *alibi,
+                               void *stream) {
+  if (!p || !alibi || nc <= 0 || nr <= 0 || nz <= 0 || n_past < 0) { set_error("attn_softmax_alibi: bad argument"); return VSIM_EINVAL; }
+  return launch_attn_softmax(p, nc, nr, nz, n_past, scale, (hipStream_t)stream, alibi, false);
+}
+int vsim_op_alibi_slopes(float *slopes_host, int n_head) {
+  if (!slopes_host || n_head <= 0) { set_error("alibi_slopes: bad argument"); return VSIM_EINVAL; }
+  alibi_slopes_host(slopes_host, n_head);
+  return VSIM_OK;
+}
+int vsim_op_kqv_causal_merged(const float *V, int ldv, const float *S, int d, int H, int nk, int n, int n_past,
+                              float *out, void *stream) {
+  if (n_past < 0) { set_error("kqv_causal_merged: n_past must be >= 0"); return VSIM_EINVAL; }
+  return launch_kqv(V, ldv, S, d, H, nk, n, out, 1, (hipStream_t)stream, n_past);
+}
 
 }  // extern "C"
 

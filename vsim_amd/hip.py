@@ -63,6 +63,8 @@ EXPORTS = [
     "vsim_op_ln_quant", "vsim_op_gemv_batch",
     "vsim_op_w4a16_ln", "vsim_op_w4a16_gelu", "vsim_op_w4a16_gemv", "vsim_w4a16_set_step",
     "vsim_op_q4_gemm_w4a16_tile", "vsim_w4a16_set_tile_gemm",
+    "vsim_op_gemm_q4_f16x", "vsim_op_rope_kv_write", "vsim_op_add_residual", "vsim_op_add_rows",
+    "vsim_op_gelu_bias", "vsim_op_attn_softmax_alibi", "vsim_op_alibi_slopes", "vsim_op_kqv_causal_merged",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -374,6 +376,14 @@ def lib():
     L.vsim_op_q4_gemm_w4a16_tile.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
     L.vsim_w4a16_set_tile_gemm.argtypes = [ci]
     L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
+    L.vsim_op_gemm_q4_f16x.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
+    L.vsim_op_rope_kv_write.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.vsim_op_add_residual.argtypes = [vp, vp, vp, ci, ci, vp]
+    L.vsim_op_add_rows.argtypes = [vp, vp, ci, vp]
+    L.vsim_op_gelu_bias.argtypes = [vp, vp, ci, vp, ci, vp]
+    L.vsim_op_attn_softmax_alibi.argtypes = [vp, ci, ci, ci, ci, cf, vp, vp]
+    L.vsim_op_alibi_slopes.argtypes = [vp, ci]
+    L.vsim_op_kqv_causal_merged.argtypes = [vp, ci, vp, ci, ci, ci, ci, ci, vp, vp]
     _lib = L
     return L
 
