@@ -271,6 +271,56 @@ int vsim_op_q4_gemm_w4a16_tile(const void *w, int M, int K, const void *x16, con
  * at every N.  All three give the same bits.  The batched step (vsim_model_decode_batch_w4a16) and
  * the single-token step are not affected.  Other values select 1.  Returns the previous value. */
 int vsim_w4a16_set_tile_gemm(int v);
+/* ---- weight-only mode: the fp16 MFMA attention (attn_w4a16.hip), opt-in.
+ *
+ * vsim_w4a16_set_attn: process-wide switch.  0 (default): the mode's attention is the exact path's
+ * (KQ with double sums, the fp16-table softmax, the KQV float chains).  1: on a graph without ALiBi
+ * with head dim 64, 96, 128 or 256 and n_embd a multiple of 64, every path of a weight-only model
+ * -- prompt, slot, vsim_model_eval_score, the batched step, the single-token step -- at every N runs
+ * the attention below; any other model, and exact and fast mode, are not affected.  The setting
+ * changes the mode's bits, not its promise (vsim_model_set_mode): a row's logits are the same bits
+ * on every path.  Other values select 0.  Models drop their captured step graphs when they next
+ * run after a change.  Returns the previous value.
+ *
+ * The contract, per row (a formula, not a kernel).  One head of D dims, a query at absolute
+ * position p, keys 0..p of that sequence's fp32 cache:
+ *   q16 = fp16(float32(q) * qs), qs = float32(scale) * float32(log2 e); k16 = fp16(k), v16 = fp16(v);
+ *   key blocks of 64 aligned to key 0 (not to n_past, not to the batch), visited 0, 1, ..., p / 64
+ *   and no others; per block S = K16 . q16 on v_mfma_f32_32x32x16_f16, chained over D / 16 steps
+ *   from C = 0, keys the A rows, queries the B columns; keys past p are left out of the maximum and
+ *   get p_k = 0 exactly; m' = max(m, block max), alpha = exp2f(m - m'), p_k = exp2f(s_k - m');
+ *   l = l alpha + sum p_k (the lane's keys in register order, then the other half-wave's sum);
+ *   O = O alpha, then O += V16^T . fp16(P)^T on the same MFMA, k-steps in key order;
+ *   y = O / l + 0.0f.
+ * Nothing a row's result depends on comes from another row: not its wave's other queries, not N,
+ * n_past, B, the slot, or cache rows past p.  Both entries run the same device code per 32-query
+ * group x 64-key block.  RoPE of q and of the new k, the fp32 cache write and the out-projection's
+ * operand (vsim_op_w4a16_rows over the whole attention row) stay the exact path's, bits included.
+ *   Stale cache rows: a slot's rows past p may hold NaN or Inf, and 0 x NaN inside the P.V MFMA is
+ *   NaN.  Rule: the V operand of a key past the sequence's last key is zero and its K operand is the
+ *   last key's row; its score is masked whatever it is.
+ *   Sign of zero: the prompt form runs a key block for every query of a wave when one of them sees
+ *   it, which adds +0 to O of a row that sees none of it and turns a -0 into +0; masked keys inside
+ *   a row's last block do the same through p x v.  Only the sign of an O that ends as zero can differ.
+ *   Rule: canonical zero -- both forms add + 0.0f after the division; y is never -0.
+ * Accuracy: tests/attn_ref.py's bound (c 2^-11 A + T, and 2e-2 max|V| against fp64).
+ *
+ * vsim_op_attn_w4a16_prompt (k_kv_f16 + k_attn_w4a16_tile): N >= 1 queries Q [N][H d] (after RoPE) at
+ * positions n_past .. n_past + N - 1 over the cache rows kc, vc [n_past + N][H d]; out [N][H d].
+ * scratch: vsim_op_attn_prefill_layout(H d, n_past + N)'s bytes, in its layout (required).
+ * VSIM_EINVAL for another head dim, H d % 64, N < 1, n_past < 0, a NULL or a short scratch.
+ *
+ * vsim_op_attn_w4a16_rows (k_attn_w4a16_rows): B rows, one new token each, every row on a cache and
+ * at a position of its own, arguments as vsim_op_attn_decode_batch's.  Per row and head: RoPE and the
+ * K / V cache row exactly as that entry writes them (no row past p is written), then the attention
+ * above over the row's fp32 cache, each 64-key block converted to fp16 on the fly; no LDS score row,
+ * so n_ctx does not bound it.  a->out is required; a->oq, a->oxd and a->alibi must be NULL;
+ * a->kqv_nth is ignored.  VSIM_EINVAL for another head dim, H d % 64, B outside 1..VSIM_BATCH_MAX or a
+ * missing pointer.  Both are enqueued on stream, not synchronized (the rows entry waits when it has
+ * to build the RoPE table itself, as vsim_op_attn_decode_batch does). */
+int vsim_w4a16_set_attn(int v);
+int vsim_op_attn_w4a16_prompt(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
+                              float scale, float *out, void *scratch, size_t scratch_bytes, void *stream);
 /* ---- weight-only mode: the kernels of the single-token step (w4a16_decode.hip).  Each is, bit for
  * bit, a composition of entries above on the same row; none has a tolerance of its own.
  *
@@ -366,6 +416,8 @@ typedef struct {
   float *oxd;               /* [B][H d] its factors d*(q-8), pair-interleaved as vsim_op_q4_quantize's */
 } vsim_attn_batch_args;
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream);
+/* weight-only mode's single-query fp16 attention on the same arguments (vsim_w4a16_set_attn above) */
+int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream);
 /* The same single-query attention for one row (a->B == 1) as the fused layer tail runs it: the
  * head role of k_layer_tail alone (704 threads per workgroup, write-through output stores, each
  * head over nsplit = 1 or 2 workgroups that halve its KQV columns), with neither an fc_out nor an
@@ -910,7 +962,9 @@ int vsim_model_randomize(vsim_model *m, uint64_t seed, float std);
  * fast prompt attention, the fp16 GEMMs and their epilogues are not used; one exception, BLOOM's
  * prompt softmax: the reference adds the ALiBi term (j + 1) m_h to row j of a batch, a per-row
  * constant that no softmax depends on except in its rounding, and this mode adds the single-token
- * step's 1 m_h to every row instead, so that a row does not depend on its place in a batch) is
+ * step's 1 m_h to every row instead, so that a row does not depend on its place in a batch; and one
+ * option, vsim_w4a16_set_attn(1): KQ, softmax and KQV on fp16 MFMA under a per-row contract of their
+ * own, with the promises below unchanged) is
  * accepted on a whole
  * model (layers [0, n_layer)) at any n_ctx; VSIM_EINVAL on a pipeline stage.  Every kernel of the
  * mode is per row, so in this mode, bit for bit:

@@ -116,6 +116,9 @@ def baseline_child_batch(a, L, h, ck):
     if a.child_mode == "fast":  # (the model is in fast mode: the fast step)
         step = L.vsim_model_decode_batch_fast
         step.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    if a.child_mode == "w4a16":  # (the weight-only step, whatever the model's mode)
+        step = L.vsim_model_decode_batch_w4a16
+        step.argtypes = [vp, ci, vp, vp, vp, vp, vp]
     bs = [int(b) for b in a.bs.split(",")]
     ck(L.vsim_model_seq_reserve(h, max(bs)), "seq_reserve")
     n, res = a.pos1 - a.pos0, {}
@@ -391,6 +394,10 @@ def main_w4a16(a):
         f"positions 0..{a.pos0 - 1} discarded as warm-up), wall clock round calls that end in a stream synchronize; "
         f"median of {a.repeats} repeats")
     res = {}
+    if a.attn == "both":
+        return main_w4a16_attn(a, dm, hip, bs, n, say, lines)
+    hip.w4a16_set_attn(1 if a.attn == "f16" else 0)
+    say(f"# the mode's attention (vsim_w4a16_set_attn): {a.attn}")
     for B in bs:
         runs = [B * n / timed_steps(dm, B, a.pos0, a.pos1, w4a16=True) for _ in range(a.repeats)]
         res[B] = statistics.median(runs)
@@ -438,9 +445,49 @@ def main_w4a16(a):
             f.write("\n".join(lines) + "\n")
 
 
+def main_w4a16_attn(a, dm, hip, bs, n, say, lines):
+    """--mode w4a16 --attn both: decode_batch_w4a16 with the attention switch at 1 (k_attn_w4a16_rows)
+    and at 0 (k_attn_decode_batch), the parent library's step, and the attention kernel's time in one
+    profiled step of each setting."""
+    res = {}
+    for sw, name in ((1, "attn f16  "), (0, "attn exact")):
+        hip.w4a16_set_attn(sw)
+        for B in bs:
+            timed_steps(dm, B, a.pos0, a.pos1, w4a16=True)  # (a warm pass)
+            runs = [B * n / timed_steps(dm, B, a.pos0, a.pos1, w4a16=True) for _ in range(a.repeats)]
+            res[sw, B] = statistics.median(runs)
+            say(f"B {B:2d}, {name}: decode_batch_w4a16 {res[sw, B]:9.1f} tok/s   (runs {' '.join(f'{v:.0f}' for v in runs)})")
+    for sw in (1, 0):
+        hip.w4a16_set_attn(sw)
+        for B in bs:
+            timed_steps(dm, B, 0, a.pos0, w4a16=True)
+            dm.set_profile(True)
+            dm.decode_batch_w4a16(list(range(B)), [a.pos0] * B, [5] * B, want_logits=False)
+            ks = dm.profile_kernels()
+            dm.set_profile(False)
+            tot = sum(k["ms"] for k in ks)
+            at = [k for k in ks if k["name"].startswith("k_attn")]
+            say(f"one profiled step, B {B:2d}, position {a.pos0}, switch {sw}: " +
+                ", ".join(f"{k['name']} {k['ms']:.3f} ms in {k['launches']} launches" for k in at) + f"; all kernels {tot:.3f} ms")
+    hip.w4a16_set_attn(0)
+    dm.close()
+    if a.baseline_lib:
+        pb = {int(k): v for k, v in run_baseline(a, a.baseline_lib, "batch", "w4a16").items()}
+        for B in bs:
+            say(f"parent commit, B {B:2d}: decode_batch_w4a16 {pb[B]['tok_s']:9.1f} tok/s   "
+                f"(runs {' '.join(f'{v:.0f}' for v in pb[B]['runs'])})   f16 / parent {res[1, B] / pb[B]['tok_s']:5.2f}   "
+                f"exact / parent {res[0, B] / pb[B]['tok_s']:5.2f}")
+    if a.out:
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="exact", choices=["exact", "fast", "w4a16"])
+    ap.add_argument("--attn", default="exact", choices=["exact", "f16", "both"],
+                    help="--mode w4a16: the mode's attention (vsim_w4a16_set_attn); both: the two settings side by side")
+    ap.add_argument("--append", action="store_true", help="--attn both: add to --out instead of replacing it")
     ap.add_argument("--score-tokens", type=int, default=2048, help="--mode w4a16: the scoring window (0: none)")
     ap.add_argument("--sample", action="store_true", help="the sampled step, both modes (see the module text)")
     ap.add_argument("--child-kind", default="generate", help=argparse.SUPPRESS)

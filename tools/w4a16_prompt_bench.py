@@ -161,6 +161,59 @@ def op_bench(say, hip, torch, repeats):
         del w, x, x16, e, ya, yb
 
 
+def attn_section(a, dm, hip, tok, N, say):
+    """--attn both: the prompt eval and the score window with the attention switch at 1
+    (k_attn_w4a16_tile) and at 0 (the exact path's KQ, softmax and KQV), the parent library, and the
+    attention's share of one profiled eval at each setting.  The exact path's three attention kernels
+    carry no profile name: their time is the profiled eval's wall clock less its named kernels."""
+    res = {}
+    for sw in (1, 0):
+        hip.w4a16_set_attn(sw)
+        e_med, e_runs, e_out = timed(lambda: dm.eval(0, tok), a.repeats)
+        s_med, s_runs, s_out = timed(lambda: dm.score(0, tok)[0], a.repeats)
+        res[sw] = dict(eval=e_med, eval_runs=e_runs, eval_hash=digest(e_out), score=s_med, score_runs=s_runs,
+                       score_hash=digest(s_out))
+    names = {1: "this library, attn f16  (switch 1)", 0: "this library, attn exact (switch 0)"}
+    if a.baseline_lib:
+        res["parent"] = run_child(a, a.baseline_lib)
+        names["parent"] = "parent commit                     "
+    for what, label in (("eval", f"Model.eval of a {N}-token prompt"), ("score", f"one {N}-token Model.score window")):
+        say(f"{label}:")
+        for k in (1, 0, "parent"):
+            if k in res:
+                r = res[k]
+                say(f"    {names[k]} {r[what] * 1e3:9.2f} ms  (runs {' '.join(f'{v * 1e3:.2f}' for v in r[what + '_runs'])}; "
+                    f"hash {r[what + '_hash']})")
+        if "parent" in res:
+            say(f"    switch 0's hash equals the parent's: {'yes' if res[0][what + '_hash'] == res['parent'][what + '_hash'] else 'NO'}")
+            slow, fast = max(res[1][what + "_runs"]), min(res["parent"][what + "_runs"])
+            say(f"    parent / switch 1: {res['parent'][what] / res[1][what]:.2f}x (medians); slowest switch-1 run {slow * 1e3:.2f} ms "
+                f"against fastest parent run {fast * 1e3:.2f} ms: {'faster' if slow < fast else 'NOT faster'}")
+        say(f"    switch 0 / switch 1: {res[0][what] / res[1][what]:.2f}x")
+    for sw in (1, 0):
+        hip.w4a16_set_attn(sw)
+        dm.eval(0, tok, want_logits=False)
+        dm.set_profile(True)
+        t0 = time.perf_counter()
+        dm.eval(0, tok, want_logits=False)
+        wall = (time.perf_counter() - t0) * 1e3
+        ks = dm.profile_kernels()
+        dm.set_profile(False)
+        tot = sum(k["ms"] for k in ks)
+        if sw:
+            at = sum(k["ms"] for k in ks if k["name"].startswith("k_attn_w4a16"))
+            say(f"one profiled {N}-token eval, switch 1: {tot:.2f} ms of named kernels, k_kv_f16 + k_attn_w4a16_tile {at:.3f} ms "
+                f"({100 * at / tot:.2f} % of them; {at / max(1, sum(k['launches'] for k in ks if k['name'].startswith('k_attn_w4a16'))):.3f} ms per layer); "
+                f"wall clock of the profiled call {wall:.2f} ms")
+        else:
+            say(f"one profiled {N}-token eval, switch 0: {tot:.2f} ms of named kernels, wall clock of the profiled call {wall:.2f} ms: "
+                f"{wall - tot:.2f} ms ({100 * (wall - tot) / wall:.1f} %) outside them -- k_kq, k_attn_softmax, k_kqv and the RoPE / cache write")
+        for k in sorted(ks, key=lambda k: -k["ms"]):
+            say(f"    {k['name']:<40s} {k['ms']:9.3f} ms  {100 * k['ms'] / tot:6.2f}%  {k['launches']:5d} launches")
+    hip.w4a16_set_attn(0)
+    dm.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="gpt-j-6B")
@@ -173,6 +226,8 @@ def main():
     ap.add_argument("--no-ops", action="store_true", help="skip the op-entry section (a second config)")
     ap.add_argument("--out", default="")
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second config)")
+    ap.add_argument("--attn", default="exact", choices=["exact", "f16", "both"],
+                    help="the mode's attention (vsim_w4a16_set_attn); both: the two settings and the parent side by side")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--lib", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -206,6 +261,11 @@ def main():
     dm.set_mode(hip.MODE_W4A16)
     tok = [int(t) for t in tokens_of(N, hp["n_vocab"])]
 
+    if a.attn == "both":
+        attn_section(a, dm, hip, tok, N, say)
+        return flush()
+    hip.w4a16_set_attn(1 if a.attn == "f16" else 0)
+    say(f"# the mode's attention (vsim_w4a16_set_attn): {a.attn}")
     res = {}
     for sw in (1, 0):
         hip.w4a16_set_tile_gemm(sw)

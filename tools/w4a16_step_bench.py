@@ -95,6 +95,39 @@ def run_child(a, lib, mode):
     return json.loads(r.stdout.strip().splitlines()[-1])
 
 
+def attn_section(a, dm, hip, generate_rate, prompt, say, lines):
+    """--attn both: the captured step with the attention switch at 1 (k_attn_w4a16_rows) and at 0
+    (k_attn_decode_batch), the parent library, and the attention kernel's time in one profiled step."""
+    res = {}
+    for sw, name in ((1, "attn f16  "), (0, "attn exact")):
+        hip.w4a16_set_attn(sw)
+        res[sw] = generate_rate(hip.MODE_W4A16, 1, True)
+        t, runs, ids, nk = res[sw]
+        say(f"this library, {name}, step on, hipGraph on {t:8.1f} tok/s  ({1e3 / t:6.3f} ms per step, {nk} launches; "
+            f"runs {' '.join(f'{v:.1f}' for v in runs)}; first ids {ids})")
+    for sw in (1, 0):
+        hip.w4a16_set_attn(sw)
+        dm.eval(0, prompt, want_logits=False)
+        dm.set_profile(True)
+        dm.eval_argmax(a.pos0, 7)
+        ks = dm.profile_kernels()
+        dm.set_profile(False)
+        tot = sum(k["ms"] for k in ks)
+        say(f"one profiled step at position {a.pos0}, switch {sw}: " +
+            ", ".join(f"{k['name']} {k['ms']:.3f} ms in {k['launches']} launches" for k in ks if k["name"].startswith("k_attn")) +
+            f"; all kernels {tot:.3f} ms")
+    hip.w4a16_set_attn(0)
+    dm.close()
+    if a.baseline_lib:
+        base = run_child(a, a.baseline_lib, "w4a16")
+        say(f"parent commit, w4a16                     {base['tok_s']:8.1f} tok/s  (runs {' '.join(f'{v:.1f}' for v in base['runs'])}; "
+            f"first ids {base['ids']}; same ids as switch 0: {'yes' if base['ids'] == res[0][2] else 'NO'})")
+        say(f"attn f16 / parent {res[1][0] / base['tok_s']:.3f}x   attn exact / parent {res[0][0] / base['tok_s']:.3f}x")
+    if a.out:
+        with open(a.out, "a" if a.append else "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="gpt-j-6B")
@@ -107,6 +140,8 @@ def main():
     ap.add_argument("--tree", default="?", help="what the tree is, for the header line")
     ap.add_argument("--out", default="")
     ap.add_argument("--append", action="store_true", help="add to --out instead of replacing it (a second config)")
+    ap.add_argument("--attn", default="exact", choices=["exact", "f16", "both"],
+                    help="the mode's attention (vsim_w4a16_set_attn); both: the two settings and the parent side by side")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--child-mode", default="w4a16", help=argparse.SUPPRESS)
     ap.add_argument("--lib", default="", help=argparse.SUPPRESS)
@@ -146,6 +181,10 @@ def main():
             runs.append(n / (time.perf_counter() - t0))
         return statistics.median(runs[1:]), runs[1:], [int(t) for t in ids[:8]], dm.info()["kernels_per_eval"]
 
+    if a.attn == "both":
+        return attn_section(a, dm, hip, generate_rate, prompt, say, lines)
+    hip.w4a16_set_attn(1 if a.attn == "f16" else 0)
+    say(f"# the mode's attention (vsim_w4a16_set_attn): {a.attn}")
     res = {}
     for name, mode, step, graph in (("step on, hipGraph on", hip.MODE_W4A16, 1, True),
                                     ("step on, hipGraph off", hip.MODE_W4A16, 1, False),

@@ -590,6 +590,14 @@ int attn_prefill_prepare() {
   return rc;
 }
 
+// k_kv_f16 over every key of [0, nk) for a caller in another file (weight-only mode's prompt attention)
+int launch_kv_f16(const float *kc, const float *vc, int E, int d, int nk, int ldt, _Float16 *k16, _Float16 *vt16,
+                  hipStream_t s) {
+  hipLaunchKernelGGL(k_kv_f16, dim3(ldt / 64, E / 64), dim3(256), 0, s, kc, vc, E, d, nk, ldt, k16, vt16, 0, 0);
+  VSIM_HIP(hipGetLastError());
+  return VSIM_OK;
+}
+
 size_t attn_prefill_scratch(int E, int nk) {
   const size_t ldt = (size_t)(nk + AP_BK - 1) / AP_BK * AP_BK;
   return 2 * ldt * E * sizeof(_Float16);

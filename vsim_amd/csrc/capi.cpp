@@ -244,6 +244,40 @@ int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
   return a->n_rot > 0 && !a->cs ? with_rope_table(a->n_ctx, a->n_rot, s, launch) : launch(D.cs);
 }
 
+// Weight-only mode's fp16 attention: the single-query form on a vsim_attn_batch_args (out required;
+// no Q4 row, no ALiBi) and the prompt form on the caller's scratch.
+int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream) {
+  if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->out || a->oq || a->oxd || a->alibi ||
+      a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || a->B < 1 ||
+      a->B > VSIM_BATCH_MAX || !attn_w4a16_supported(a->d, a->d * a->H)) {
+    set_error("attn_w4a16_rows: bad argument (head dim 64, 96, 128 or 256, n_embd a multiple of 64, 1..32 rows, out "
+              "given, oq / oxd / alibi NULL)");
+    return VSIM_EINVAL;
+  }
+  AttnJob A{};
+  A.q = a->q;
+  A.k = a->k;
+  A.v = a->v;
+  A.d = a->d;
+  A.H = a->H;
+  A.n_rot = a->n_rot;
+  A.style = a->style;
+  A.n_ctx = a->n_ctx;
+  A.scale = a->scale;
+  A.out = a->out;
+  hipStream_t s = (hipStream_t)stream;
+  const AttnRows R{a->kc, a->vc, 0, a->n_past};
+  auto launch = [&](const double2 *cs) {
+    A.cs = cs;
+    return launch_attn_w4a16_rows(A, R, a->B, s);
+  };
+  return a->n_rot > 0 && !a->cs ? with_rope_table(a->n_ctx, a->n_rot, s, launch) : launch((const double2 *)a->cs);
+}
+int vsim_op_attn_w4a16_prompt(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
+                              float scale, float *out, void *scratch, size_t scratch_bytes, void *stream) {
+  return launch_attn_w4a16_tile(Q, kc, vc, d, H, N, n_past, scale, out, (hipStream_t)stream, scratch, scratch_bytes);
+}
+
 // The heads of k_layer_tail alone (attn_body<704, true>: 11 waves, write-through stores, nsplit
 // workgroups per head): launch_layer_tail with neither an fc_out nor an out-projection job, so
 // every workgroup takes the head role, on flags and an epoch word of the call's own (epoch 1, layer 0).

@@ -464,6 +464,18 @@ int attn_prefill_ldt(int nk);  // V^T row length (keys padded to the key tile)
 _Float16 *attn_prefill_k16(void *scratch, int E, int nk);
 _Float16 *attn_prefill_vt16(void *scratch, int E, int nk);
 size_t attn_prefill_scratch(int E, int nk);
+// k_kv_f16 alone: keys [0, nk) of a layer's cache into the K16 / V^T images (ldt = attn_prefill_ldt(nk))
+int launch_kv_f16(const float *kc, const float *vc, int E, int d, int nk, int ldt, _Float16 *k16, _Float16 *vt16,
+                  hipStream_t s);
+// Weight-only mode's fp16 MFMA attention (attn_w4a16.hip; the per-row contract is in its header and
+// in vsim_hip.h): the prompt form over the K16 / V^T scratch (attn_prefill_scratch(E, n_past + N)
+// bytes, required) and the single-query form over B rows with a cache and a position each (A and R
+// as launch_attn_decode_batch's; A.out required, A.oq_* / A.oxd / A.kqv_nth / A.etab unused, no ALiBi).
+bool attn_w4a16_supported(int d, int E);  // d in {64, 96, 128, 256} and E % 64 == 0
+int attn_w4a16_prepare();                 // the kernels' LDS attributes, once
+int launch_attn_w4a16_tile(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
+                           float scale, float *out, hipStream_t s, void *scratch, size_t scratch_bytes);
+int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s);
 // The heads' completion flags of the layer tail (r06): one 8-byte {unused, tag} sc1 granule per head
 // workgroup, tag = epoch << 8 | layer + 1 (the epoch advanced by the step's first k_ln_quant), so
 // no counter has to be zeroed between layers or steps

@@ -763,6 +763,8 @@ struct PromptBatch {
 // fc_in (+bias) -> GELU -> fc_out (+bias) -> residual join (GPT-NeoX: vsim.cpp:526-695; BLOOM:
 // oracle eval_bloom, inpFF = attn + inpL -> LN -> w1 -> GELU -> w2 -> inpL = ff + inpFF).  What
 // differs between them is GraphDesc's.
+bool w4a16_attn16(const vsim_model *m);  // (below, with the mode's switches)
+
 int run_layer(PromptBatch &B, int il) {
   vsim_model *m = B.m;
   const GraphDesc &G = m->gd;
@@ -789,7 +791,10 @@ int run_layer(PromptBatch &B, int il) {
   // then converts only the cached keys before them.  (ALiBi lives in the softmax kernel only:
   // BLOOM keeps the KQ / softmax / KQV kernels in both modes.)
   const bool attn16 = !rows && !G.alibi && D.mode == VSIM_MODE_FAST && N >= 8 && attn_prefill_supported(d) && E % 64 == 0;
-  if (attn16) RC(ensure_pf_scratch(m));
+  // weight-only mode's fp16 attention (attn_w4a16.hip, vsim_w4a16_set_attn): every path of the model
+  // at every N, the prompt kinds on the tile form, the rows kind on the single-query form
+  const bool wattn = w4a16 && w4a16_attn16(m);
+  if (attn16 || (wattn && !rows)) RC(ensure_pf_scratch(m));
   const bool kv16_epi = rope_epi && attn16;
   G2Epi ek = er, ev;
   if (kv16_epi) {
@@ -826,7 +831,10 @@ int run_layer(PromptBatch &B, int il) {
     AttnJob A = attn_job(decode_attn_desc(m, tab, ActRow{q4_rows(m->xq2, E, N), m->xd2}, 1), nullptr, nullptr, nullptr);
     if (w4a16) A.out = m->attn_in;  // the out-projection's operand is made from the f32 row
     const AttnRows R{D.rows->kc, D.rows->vc, loff, D.rows->npast};
-    LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
+    if (wattn)
+      LAUNCH(m, nk, launch_attn_w4a16_rows(A, R, N, s), "k_attn_w4a16_rows", 0.0);
+    else
+      LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
   } else if (!rope_epi) {
     RC(launch_rope_kv_write(G.rotary == ROT_GPTJ ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past,
                             G.rotary == ROT_NONE ? 0 : m->hp.n_rot, m->rope_cs, s));
@@ -843,6 +851,10 @@ int run_layer(PromptBatch &B, int il) {
     RC(launch_attn_prefill_f16(m->Qb, kc, vc, d, H, N, n_past, scale, m->attn_in, s, m->pf_scratch, m->pf_bytes,
                                kv16_epi, attn_q16 ? B.xb : nullptr));
     nk += 2;
+  } else if (wattn) {
+    LAUNCH(m, nk, launch_attn_w4a16_tile(m->Qb, kc, vc, d, H, N, n_past, scale, m->attn_in, s, m->pf_scratch, m->pf_bytes),
+           "k_attn_w4a16_tile", 2.0 * nkv * E * sizeof(float));
+    ++nk;  // (k_kv_f16 before it)
   } else {
     RC(launch_kq(kc, E, m->Qb, E, d, H, nkv, N, m->kq, s, n_past)); ++nk;
     RC(launch_attn_softmax(m->kq, nkv, N, H, n_past, scale, s, G.alibi ? m->alibi : nullptr, w4a16)); ++nk;
@@ -1206,6 +1218,14 @@ bool w4a16_step_ok(const vsim_model *m) {
 bool w4a16_general(const vsim_model *m) {
   return m->mode == VSIM_MODE_W4A16 && !(g_w4a16_step.load() && w4a16_step_ok(m));
 }
+// Process-wide switch of the mode's attention (vsim_w4a16_set_attn): 0 the exact path's kernels, 1
+// the fp16 MFMA attention of attn_w4a16.hip on the graphs and shapes it takes.  One answer per model
+// for all of its paths -- prompt, slot, rows batch, single-token step -- so that none mixes the two.
+std::atomic<int> g_w4a16_attn{0};
+bool w4a16_attn16(const vsim_model *m) {
+  const int E = m->hp.n_embd, d = E / m->hp.n_head;
+  return m->mode == VSIM_MODE_W4A16 && g_w4a16_attn.load() && !m->gd.alibi && attn_w4a16_supported(d, E);
+}
 
 int enqueue_decode_w4a16(vsim_model *m, int &nk) {
   const int E = m->hp.n_embd, F = 4 * E, V = m->hp.n_vocab;
@@ -1250,7 +1270,10 @@ int enqueue_decode_w4a16(vsim_model *m, int &nk) {
     AttnJob A = attn_job(decode_attn_desc(m, tab, ra, 1), nullptr, nullptr, nullptr);
     A.out = m->attn_in;
     const AttnRows R{m->w4_kv, m->w4_kv + 1, loff, m->npast_dev};
-    LAUNCH(m, nk, launch_attn_decode_batch(A, R, 1, m->n_ctx, s), "k_attn_decode_batch", kv_bytes);
+    if (w4a16_attn16(m))
+      LAUNCH(m, nk, launch_attn_w4a16_rows(A, R, 1, s), "k_attn_w4a16_rows", kv_bytes);
+    else
+      LAUNCH(m, nk, launch_attn_decode_batch(A, R, 1, m->n_ctx, s), "k_attn_decode_batch", kv_bytes);
     LAUNCH(m, nk, launch_w4a16_rows(m->attn_in, E, 1, xa.h, xa.e, s), "k_w4a16_rows", (double)E * 6);
     if (serial) {
       // cur2 = attn + inpL, the MLP's input (BLOOM: and the residual)
@@ -1836,6 +1859,12 @@ int vsim_model_set_mode(vsim_model *m, int mode) {
   return VSIM_OK;
 }
 
+int vsim_w4a16_set_attn(int v) {
+  const int on = v == 1 ? 1 : 0, old = g_w4a16_attn.exchange(on);
+  if (old != on) ++g_w4a16_gen;
+  return old;
+}
+
 int vsim_w4a16_set_step(int enable) {
   const int on = enable ? 1 : 0, old = g_w4a16_step.exchange(on);
   if (old != on) ++g_w4a16_gen;
@@ -1947,6 +1976,7 @@ int decode_graph(vsim_model *m, StepKind kind) {
   }
   if (g.exec && g.mode == m->mode) return VSIM_OK;
   drop(g);
+  if (w4a16_attn16(m)) RC(attn_w4a16_prepare());  // (kernel attributes: not inside a capture)
   VSIM_HIP(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
   int nk = 0;
   const int rc = enqueue_step(m, kind, nk);

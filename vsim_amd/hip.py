@@ -63,6 +63,7 @@ EXPORTS = [
     "vsim_op_ln_quant", "vsim_op_gemv_batch",
     "vsim_op_w4a16_ln", "vsim_op_w4a16_gelu", "vsim_op_w4a16_gemv", "vsim_w4a16_set_step",
     "vsim_op_q4_gemm_w4a16_tile", "vsim_w4a16_set_tile_gemm",
+    "vsim_w4a16_set_attn", "vsim_op_attn_w4a16_prompt", "vsim_op_attn_w4a16_rows",
     "vsim_op_gemm_q4_f16x", "vsim_op_rope_kv_write", "vsim_op_add_residual", "vsim_op_add_rows",
     "vsim_op_gelu_bias", "vsim_op_attn_softmax_alibi", "vsim_op_alibi_slopes", "vsim_op_kqv_causal_merged",
 ]
@@ -375,6 +376,9 @@ def lib():
     L.vsim_w4a16_set_step.argtypes = [ci]
     L.vsim_op_q4_gemm_w4a16_tile.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp]
     L.vsim_w4a16_set_tile_gemm.argtypes = [ci]
+    L.vsim_w4a16_set_attn.argtypes = [ci]
+    L.vsim_op_attn_w4a16_prompt.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, sz, vp]
+    L.vsim_op_attn_w4a16_rows.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
     L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
     L.vsim_op_gemm_q4_f16x.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.vsim_op_rope_kv_write.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
@@ -610,6 +614,40 @@ def w4a16_set_step(enable) -> int:
     """Weight-only mode's single-token step on (default) or off (every single-token call on the
     general path); same bits either way.  Process-wide; returns the previous setting."""
     return int(lib().vsim_w4a16_set_step(int(enable)))
+
+
+def w4a16_set_attn(v) -> int:
+    """vsim_w4a16_set_attn: weight-only mode's attention, 0 (default) the exact path's kernels, 1 the
+    fp16 MFMA attention under its per-row contract on the models that take it (no ALiBi, head dim 64,
+    96, 128 or 256, n_embd a multiple of 64).  Changes the mode's bits, not its promise.
+    Process-wide; returns the previous setting."""
+    return int(lib().vsim_w4a16_set_attn(int(v)))
+
+
+def attn_prefill_layout(E, nk):
+    """vsim_op_attn_prefill_layout: (bytes, V^T offset in halves, ldt) of the K16 / V^T scratch."""
+    b, o, l = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_int()
+    check(lib().vsim_op_attn_prefill_layout(int(E), int(nk), ctypes.byref(b), ctypes.byref(o), ctypes.byref(l)),
+          "attn_prefill_layout")
+    return b.value, o.value, l.value
+
+
+def attn_w4a16_prompt(Q, kc, vc, d, H, N, n_past, scale, out, scratch, scratch_bytes=None, stream=None):
+    """vsim_op_attn_w4a16_prompt on device buffers (torch tensors): the weight-only fp16 attention of
+    N >= 1 queries Q [N][H d] (after RoPE) at positions n_past.. over the cache rows kc, vc
+    [n_past + N][H d] into out [N][H d]; scratch a byte tensor of attn_prefill_layout(H d, n_past + N)'s
+    size.  Enqueued on `stream`, not synchronized."""
+    nb = int(scratch.numel() * scratch.element_size()) if scratch_bytes is None else int(scratch_bytes)
+    check(lib().vsim_op_attn_w4a16_prompt(ptr(Q), ptr(kc), ptr(vc), d, H, N, n_past, float(scale), ptr(out),
+                                          ptr(scratch), nb, stream), "attn_w4a16_prompt")
+
+
+def attn_w4a16_rows(q, k, v, kc, vc, n_past, cs, B, d, H, n_rot, style, n_ctx, scale, out, stream=None):
+    """vsim_op_attn_w4a16_rows on device buffers (torch tensors): attn_decode_batch's arguments without
+    ALiBi and the Q4 row; out [B][H d] is required."""
+    a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), None, B, d, H, n_rot,
+                      style, n_ctx, 0, float(scale), ptr(out), None, None)
+    check(lib().vsim_op_attn_w4a16_rows(ctypes.byref(a), stream), "attn_w4a16_rows")
 
 
 def batch_set_fast_gemm(enable) -> int:

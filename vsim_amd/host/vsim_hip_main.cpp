@@ -6,7 +6,7 @@
 // (prompt echoed in n_batch+1 chunks, then sampled ids), " <END|>"; --return_logits
 // prints "logits: %.8f ..." rows.  The model runs in libvsim_hip.so (device resident);
 // this file is host control only: the sampler too is the library's (vsim_sampler_*).
-// Extra flags: --device N, --mode exact|fast|w4a16, --n_ctx N (reference: fixed 512,
+// Extra flags: --device N, --mode exact|fast|w4a16, --attn exact|f16 (with w4a16), --n_ctx N (reference: fixed 512,
 // vsim.cpp:758), --no-graph, --sampler host|device, --quantize (load an F32 / F16 file as the
 // converters write it, quantized to Q4_0 on the device while it loads), --score (the -p ids are a
 // text to score: per-position log-probabilities and the perplexity, vsim_model_eval_score).
@@ -39,6 +39,7 @@ struct Params {
   bool return_logits = false;
   int device = 0;
   int mode = VSIM_MODE_EXACT;
+  bool attn_f16 = false;  // --attn f16: vsim_w4a16_set_attn(1)
   int n_ctx = 512;
   bool graph = true;
   bool device_sampler = true;
@@ -63,6 +64,8 @@ void usage(const char *argv0, const Params &p) {
   fprintf(stderr, "  --mode exact|fast|w4a16  exact = bit-identical to the reference (default); w4a16 = weight-only:\n");
   fprintf(stderr, "                        Q4_0 weights, activations rounded to fp16 instead of quantized (generation\n");
   fprintf(stderr, "                        and --score)\n");
+  fprintf(stderr, "  --attn exact|f16      with --mode w4a16: the mode's attention, exact = the exact path's kernels (default),\n");
+  fprintf(stderr, "                        f16 = fp16 MFMA attention under its per-row contract (other bits, same promise)\n");
   fprintf(stderr, "  --n_ctx N             context length (default 512, as the reference)\n");
   fprintf(stderr, "  --no-graph            launch every kernel eagerly\n");
   fprintf(stderr, "  --quantize            the model file is F32 / F16: quantize it to Q4_0 on the GPU while loading\n");
@@ -100,6 +103,14 @@ bool parse(int argc, char **argv, Params &p) {
     else if (a == "--mode") {
       const std::string v = next();
       p.mode = v == "fast" ? VSIM_MODE_FAST : v == "w4a16" ? VSIM_MODE_W4A16 : VSIM_MODE_EXACT;
+    }
+    else if (a == "--attn") {
+      const std::string v = next();
+      if (v != "exact" && v != "f16") {
+        fprintf(stderr, "error: --attn takes exact or f16\n");
+        exit(1);
+      }
+      p.attn_f16 = v == "f16";
     }
     else if (a == "--n_ctx") p.n_ctx = std::stoi(next());
     else if (a == "--no-graph") p.graph = false;
@@ -226,6 +237,7 @@ int run(const Params &params, int arch) {
     fprintf(stderr, "%s: failed to load model from '%s': %s\n", __func__, params.model.c_str(), vsim_last_error());
     return 1;
   }
+  vsim_w4a16_set_attn(params.attn_f16 ? 1 : 0);  // (weight-only mode only; the other modes never see it)
   if (vsim_model_set_mode(model, params.mode) != VSIM_OK) {
     fprintf(stderr, "%s: --mode: %s\n", __func__, vsim_last_error());
     vsim_model_free(model);
