@@ -418,6 +418,20 @@ typedef struct {
 int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream);
 /* weight-only mode's single-query fp16 attention on the same arguments (vsim_w4a16_set_attn above) */
 int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream);
+/* Runs of rows: the two entries above for batches whose rows may share a cache, provided the rows
+ * that share one sit at distinct positions -- a run is len >= 1 consecutive tokens of one sequence as
+ * len consecutive rows at positions p, p + 1, .., p + len - 1 of its cache.  Two launches on the
+ * stream, no waits between workgroups: k_kv_rows does RoPE of every row's new key at the row's
+ * position and writes every row's K and V cache rows (the heads' own arithmetic and bits, from one
+ * shared device function), then k_attn_decode_runs / k_attn_w4a16_runs, the same heads without their
+ * cache writes, RoPE q and read keys and values 0..n_past[b] of the row's cache, its own included.
+ * A row never reads a cache row past its own position (the fp16 form clamps K and zeroes V there),
+ * so row j of a run has bit for bit the out / oq / oxd that vsim_op_attn_decode_batch /
+ * vsim_op_attn_w4a16_rows give it as the only row of a call made after rows 0..j-1 were stepped one
+ * call at a time, and the cache rows written are the same.  Arguments and errors as the entry's
+ * above. */
+int vsim_op_attn_decode_runs(const vsim_attn_batch_args *a, void *stream);
+int vsim_op_attn_w4a16_runs(const vsim_attn_batch_args *a, void *stream);
 /* The same single-query attention for one row (a->B == 1) as the fused layer tail runs it: the
  * head role of k_layer_tail alone (704 threads per workgroup, write-through output stores, each
  * head over nsplit = 1 or 2 workgroups that halve its KQV columns), with neither an fc_out nor an
@@ -1124,6 +1138,30 @@ int vsim_model_decode_batch_sample(vsim_model *m, int mode, int B, const int32_t
 int vsim_model_decode_batch_sample_w4a16(vsim_model *m, int B, const int32_t *seq, const int32_t *n_past,
                                          const int32_t *tokens, vsim_sampler *const *samplers /* [B] */,
                                          int32_t *next /* host [B] */);
+/* The batched step with a run of tokens per slot.  S slots; slot seq[s] contributes len[s] >= 1
+ * consecutive tokens at positions n_past[s], n_past[s] + 1, .., n_past[s] + len[s] - 1, the runs
+ * concatenated in `tokens` in slot order, N = sum len <= VSIM_BATCH_MAX rows in all; logits and next
+ * have one row per token in that order.  mode is VSIM_MODE_EXACT, VSIM_MODE_FAST or VSIM_MODE_W4A16
+ * and names the products exactly as vsim_model_decode_batch, _fast and _w4a16 do (exact is refused
+ * on a model that is not in exact mode).  The weights stream once for all N rows.  Every layer's
+ * attention is the two launches of vsim_op_attn_decode_runs (vsim_op_attn_w4a16_runs under
+ * vsim_w4a16_set_attn(1) in weight-only mode); everything else is the batched step's.
+ * Contract, in every mode: row j of slot s is bit for bit row 0 of the vsim_model_decode_batch* call
+ * that `mode` names with B = 1 on that slot at n_past[s] + j, after the j rows before it were stepped
+ * the same way, and the cache rows written are the same -- for every S, every mix of lengths and
+ * positions and whatever shares the batch.  Greedy speculative decoding follows: feed [last token] +
+ * draft as one run, and next[i] is the plain loop's token after row i wherever rows 1..i were the
+ * plain loop's own tokens.
+ * Rollback: a step never reads a cache row at or past the position it runs at, so after a rejected
+ * draft the caller just continues from a smaller n_past; the rows the rejected tokens wrote are
+ * overwritten before anything reads them.
+ * VSIM_EINVAL, with nothing enqueued: S < 1, len[s] < 1, N > VSIM_BATCH_MAX, a slot outside the
+ * reserve or named twice (one run per slot), n_past[s] < 0 or n_past[s] + len[s] > n_ctx, a token
+ * outside the vocabulary, another mode value, a model that is not a whole model.  VSIM_ESPIN as
+ * vsim_model_eval.  Enqueued eagerly (no hipGraph), one wait at the end. */
+int vsim_model_decode_runs(vsim_model *m, int mode, int S, const int32_t *seq, const int32_t *n_past,
+                           const int32_t *len, const int32_t *tokens /* [N], N = sum len, runs concatenated */,
+                           float *logits /* host [N][n_vocab] or NULL */, int32_t *next /* host [N] or NULL */);
 /* Slot fork: cache rows [0, n_tokens) of K and V of every layer go from slot src to slot dst
  * (device to device on the model's stream, one strided copy each; ordered with the steps before
  * and after it, not synchronized).  A slot holds nothing but these rows, so dst then continues

@@ -30,7 +30,11 @@ constexpr int ATT_DPL = 4;      // max float4 of the head dimension per lane in 
 // and softmax (identical in each), then the KQV chains and quantization of output columns
 // [part*c, part*c + c), c = d / S, so a head's V rows spread over S CUs.  Every part writes
 // the same new K/V cache row (identical bytes) before reading it back.
-template <int NT, bool CO = false>
+// KW (the default): the head RoPEs the new key, writes the row's K / V cache rows and reads them back,
+// as above.  KW = false, the run steps' head (k_attn_decode_runs): RoPE of q only and no store to
+// the caches -- k_kv_rows wrote the rows of every row of the batch in the launch before -- then keys
+// and values 0..n_past from the cache, the row's own included, through the same code.
+template <int NT, bool CO = false, bool KW = true>
 __device__ __forceinline__ void attn_body(const AttnJob &A, int hs, float *sm) {
   constexpr int ATT_THREADS = NT, ATT_WAVES = NT / 64;
   const int S = A.nsplit > 1 ? A.nsplit : 1, h = hs / S, part = hs % S;
@@ -45,34 +49,22 @@ __device__ __forceinline__ void attn_body(const AttnJob &A, int hs, float *sm) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   for (int i = tid; i < d; i += ATT_THREADS) {
     qh[i] = A.q[h * d + i];
-    kh[i] = A.k[h * d + i];
-    A.vc[(size_t)n_past * E + h * d + i] = A.v[h * d + i];
-  }
-  __syncthreads();
-  // RoPE (ggml.c:6117-6152 / 5952-5973), position p = n_past for both q (mode 0) and k
-  const int half = A.n_rot / 2;
-  for (int j = tid; j < half; j += ATT_THREADS) {
-    const double2 c = A.cs[(size_t)n_past * half + j];
-    const int i0 = A.style == 0 ? j : 2 * j, i1 = A.style == 0 ? j + half : 2 * j + 1;
-    const double q0 = qh[i0], q1 = qh[i1], k0 = kh[i0], k1 = kh[i1];
-    if (A.style == 0) {
-      qh[i0] = (float)(c.x * q0 - c.y * q1);
-      qh[i1] = (float)(c.x * q1 + c.y * q0);
-      kh[i0] = (float)(c.x * k0 - c.y * k1);
-      kh[i1] = (float)(c.x * k1 + c.y * k0);
-    } else {
-      qh[i0] = (float)(q0 * c.x - q1 * c.y);
-      qh[i1] = (float)(q0 * c.y + q1 * c.x);
-      kh[i0] = (float)(k0 * c.x - k1 * c.y);
-      kh[i1] = (float)(k0 * c.y + k1 * c.x);
+    if constexpr (KW) {
+      kh[i] = A.k[h * d + i];
+      A.vc[(size_t)n_past * E + h * d + i] = A.v[h * d + i];
     }
   }
   __syncthreads();
-  for (int i = tid; i < d; i += ATT_THREADS) A.kc[(size_t)n_past * E + h * d + i] = kh[i];
-  // The new key's row is read back below by whichever wave holds key n_past (wave n_past/16 %
-  // waves), not only by the threads that stored it: the barrier (its release drains the stores)
-  // orders them.  r05: until then that read raced the store whenever n_past >= 16.
+  // RoPE (kern.hpp rope_head), position p = n_past for both q (mode 0) and k
+  rope_head<true, KW>(qh, kh, A.cs, A.n_rot, A.style, n_past, tid, ATT_THREADS);
   __syncthreads();
+  if constexpr (KW) {
+    for (int i = tid; i < d; i += ATT_THREADS) A.kc[(size_t)n_past * E + h * d + i] = kh[i];
+    // The new key's row is read back below by whichever wave holds key n_past (wave n_past/16 %
+    // waves), not only by the threads that stored it: the barrier (its release drains the stores)
+    // orders them.  r05: until then that read raced the store whenever n_past >= 16.
+    __syncthreads();
+  }
   ATT_STAMP(0);
   // KQ[k] = (float) sum_i (double)(K[k][i] * q[i]) in order i = 0..d-1; then * scale.
   // Row r (lanes 16r..16r+15) of a wave takes one key per step; lane l16 covers the float4s

@@ -257,8 +257,11 @@ __global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_tile(const float *__r
 // vt_pos order, V zero and K clamped past p) and wave 0 runs the shared phases with its one query
 // in all 32 columns.  No LDS score row: n_ctx does not bound it.  (One wave computes: the key
 // blocks of a row are a chain, and 31 of the MFMA's 32 query columns are idle as it is.)
-template <int D>
-__global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_rows(AttnJob A, AttnRows R, float qscale) {
+// KW = false (k_attn_w4a16_runs, rows that may share a cache): RoPE of q only and no cache store --
+// k_kv_rows wrote every row's K / V rows in the launch before; a run's later rows lie past p, where
+// K is clamped and V zeroed as for any stale row.
+template <int D, bool KW>
+__device__ __forceinline__ void aw_rows_body(AttnJob A, AttnRows R, float qscale) {
   constexpr int KLD = aw_kld(D), VLD = AW_VLD, NT = D / 32;
   extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
   _Float16 *Ks = lds, *Vt = lds + AW_BK * KLD;
@@ -266,35 +269,23 @@ __global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_rows(AttnJob A, AttnR
   const int h = blockIdx.x, b = blockIdx.y, E = D * A.H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, hl = lane >> 5;
-  const float *q = A.q + (size_t)b * E, *k = A.k + (size_t)b * E, *v = A.v + (size_t)b * E;
+  const float *q = A.q + (size_t)b * E;
+  [[maybe_unused]] const float *k = A.k + (size_t)b * E, *v = A.v + (size_t)b * E;
   float *kc = R.kc[b] + R.loff, *vc = R.vc[b] + R.loff;
   const int p = R.npast[b];
   for (int i = tid; i < D; i += AW_THREADS) {
     qh[i] = q[h * D + i];
-    kh[i] = k[h * D + i];
-    vc[(size_t)p * E + h * D + i] = v[h * D + i];
-  }
-  __syncthreads();
-  // RoPE (attn.hpp: ggml.c:6117-6152 / 5952-5973), position p for both q and k
-  const int half = A.n_rot / 2;
-  for (int j = tid; j < half; j += AW_THREADS) {
-    const double2 c = A.cs[(size_t)p * half + j];
-    const int i0 = A.style == 0 ? j : 2 * j, i1 = A.style == 0 ? j + half : 2 * j + 1;
-    const double q0 = qh[i0], q1 = qh[i1], k0 = kh[i0], k1 = kh[i1];
-    if (A.style == 0) {
-      qh[i0] = (float)(c.x * q0 - c.y * q1);
-      qh[i1] = (float)(c.x * q1 + c.y * q0);
-      kh[i0] = (float)(c.x * k0 - c.y * k1);
-      kh[i1] = (float)(c.x * k1 + c.y * k0);
-    } else {
-      qh[i0] = (float)(q0 * c.x - q1 * c.y);
-      qh[i1] = (float)(q0 * c.y + q1 * c.x);
-      kh[i0] = (float)(k0 * c.x - k1 * c.y);
-      kh[i1] = (float)(k0 * c.y + k1 * c.x);
+    if constexpr (KW) {
+      kh[i] = k[h * D + i];
+      vc[(size_t)p * E + h * D + i] = v[h * D + i];
     }
   }
   __syncthreads();
-  for (int i = tid; i < D; i += AW_THREADS) kc[(size_t)p * E + h * D + i] = kh[i];
+  // RoPE (kern.hpp rope_head, the exact heads' lines), position p for both q and k
+  rope_head<true, KW>(qh, kh, A.cs, A.n_rot, A.style, p, tid, AW_THREADS);
+  __syncthreads();
+  if constexpr (KW)
+    for (int i = tid; i < D; i += AW_THREADS) kc[(size_t)p * E + h * D + i] = kh[i];
   whalf8 qf[D / 16];
   aw_qfrag<D>(qh, qscale, hl, qf);
   wf32x16 o[NT];
@@ -377,6 +368,16 @@ __global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_rows(AttnJob A, AttnR
   if (wave == 0 && r == 0) aw_store<D>(o, lrow, hl, A.out + (size_t)b * E + h * D);
 }
 
+template <int D>
+__global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_rows(AttnJob A, AttnRows R, float qscale) {
+  aw_rows_body<D, true>(A, R, qscale);
+}
+
+template <int D>
+__global__ void __launch_bounds__(AW_THREADS) k_attn_w4a16_runs(AttnJob A, AttnRows R, float qscale) {
+  aw_rows_body<D, false>(A, R, qscale);
+}
+
 namespace {
 
 template <int D>
@@ -395,6 +396,9 @@ bool aw_prepare_d() {
                              (int)aw_tile_lds<D>()) == hipSuccess &&
          hipFuncSetAttribute((const void *)k_attn_w4a16_rows<D>, hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)aw_rows_lds<D>()) == hipSuccess &&
+         hipFuncSetAttribute((const void *)k_attn_w4a16_runs<D>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)aw_rows_lds<D>()) == hipSuccess &&
+         hipFuncGetAttributes(&fa, (const void *)k_attn_w4a16_runs<D>) == hipSuccess &&
          hipFuncGetAttributes(&fa, (const void *)k_attn_w4a16_tile<D>) == hipSuccess &&
          hipFuncGetAttributes(&fa, (const void *)k_attn_w4a16_rows<D>) == hipSuccess;
 }
@@ -447,7 +451,7 @@ int launch_attn_w4a16_tile(const float *Q, const float *kc, const float *vc, int
   return VSIM_OK;
 }
 
-int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s) {
+int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s, bool runs) {
   if (!attn_w4a16_supported(A.d, A.d * A.H) || A.H <= 0) {
     set_error("attn_w4a16_rows: head dim 64, 96, 128 or 256 and n_embd a multiple of 64");
     return VSIM_EINVAL;
@@ -460,7 +464,13 @@ int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream
   if (int rc = attn_w4a16_prepare()) return rc;
   const float qscale = A.scale * 1.4426950408889634f;
   const dim3 grid(A.H, B);
-#define AWR(DD) hipLaunchKernelGGL(k_attn_w4a16_rows<DD>, grid, dim3(AW_THREADS), aw_rows_lds<DD>(), s, A, R, qscale)
+  if (runs)
+    if (int rc = launch_kv_rows(A, R, B, s)) return rc;
+#define AWR(DD)                                                                                                \
+  if (runs)                                                                                                    \
+    hipLaunchKernelGGL(k_attn_w4a16_runs<DD>, grid, dim3(AW_THREADS), aw_rows_lds<DD>(), s, A, R, qscale);     \
+  else                                                                                                         \
+    hipLaunchKernelGGL(k_attn_w4a16_rows<DD>, grid, dim3(AW_THREADS), aw_rows_lds<DD>(), s, A, R, qscale)
   switch (A.d) {
     case 64: AWR(64); break;
     case 96: AWR(96); break;
@@ -470,6 +480,10 @@ int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream
 #undef AWR
   VSIM_HIP(hipGetLastError());
   return VSIM_OK;
+}
+
+int launch_attn_w4a16_runs(const AttnJob &A, const AttnRows &R, int B, hipStream_t s) {
+  return launch_attn_w4a16_rows(A, R, B, s, true);
 }
 
 }  // namespace vsim

@@ -226,10 +226,13 @@ int vsim_op_w4a16_gemv(const vsim_w4a16_gemv_args *a, void *stream) {
 }
 int vsim_batch_set_gemm(int enable) { return batch_set_gemm(enable); }
 int vsim_batch_set_fast_gemm(int enable) { return batch_set_fast_gemm(enable); }
-int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
+namespace {
+// vsim_op_attn_decode_batch, and with runs vsim_op_attn_decode_runs: the same arguments and checks,
+// k_kv_rows + k_attn_decode_runs in place of the one launch
+int attn_rows_op(const vsim_attn_batch_args *a, void *stream, bool runs) {
   AttnDesc D;
   if (!attn_desc(a, 1, &D)) {
-    set_error("attn_decode_batch: bad argument");
+    set_error(runs ? "attn_decode_runs: bad argument" : "attn_decode_batch: bad argument");
     return VSIM_EINVAL;
   }
   DevTables tab;
@@ -239,19 +242,25 @@ int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) {
   const AttnRows R{a->kc, a->vc, 0, a->n_past};
   auto launch = [&](const double2 *cs) {
     D.cs = cs;
-    return launch_attn_decode_batch(attn_job(D, nullptr, nullptr, nullptr), R, a->B, a->n_ctx, s);
+    return launch_attn_decode_batch(attn_job(D, nullptr, nullptr, nullptr), R, a->B, a->n_ctx, s, runs);
   };
   return a->n_rot > 0 && !a->cs ? with_rope_table(a->n_ctx, a->n_rot, s, launch) : launch(D.cs);
 }
+}  // namespace
+int vsim_op_attn_decode_batch(const vsim_attn_batch_args *a, void *stream) { return attn_rows_op(a, stream, false); }
+int vsim_op_attn_decode_runs(const vsim_attn_batch_args *a, void *stream) { return attn_rows_op(a, stream, true); }
 
 // Weight-only mode's fp16 attention: the single-query form on a vsim_attn_batch_args (out required;
 // no Q4 row, no ALiBi) and the prompt form on the caller's scratch.
-int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream) {
+namespace {
+int attn_w4a16_rows_op(const vsim_attn_batch_args *a, void *stream, bool runs) {
   if (!a || !a->q || !a->k || !a->v || !a->kc || !a->vc || !a->n_past || !a->out || a->oq || a->oxd || a->alibi ||
       a->d <= 0 || a->H <= 0 || a->n_ctx <= 0 || a->n_rot < 0 || a->n_rot > a->d || a->n_rot % 2 || a->B < 1 ||
       a->B > VSIM_BATCH_MAX || !attn_w4a16_supported(a->d, a->d * a->H)) {
-    set_error("attn_w4a16_rows: bad argument (head dim 64, 96, 128 or 256, n_embd a multiple of 64, 1..32 rows, out "
-              "given, oq / oxd / alibi NULL)");
+    set_error(runs ? "attn_w4a16_runs: bad argument (head dim 64, 96, 128 or 256, n_embd a multiple of 64, 1..32 "
+                     "rows, out given, oq / oxd / alibi NULL)"
+                   : "attn_w4a16_rows: bad argument (head dim 64, 96, 128 or 256, n_embd a multiple of 64, 1..32 rows, out "
+                     "given, oq / oxd / alibi NULL)");
     return VSIM_EINVAL;
   }
   AttnJob A{};
@@ -269,10 +278,13 @@ int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream) {
   const AttnRows R{a->kc, a->vc, 0, a->n_past};
   auto launch = [&](const double2 *cs) {
     A.cs = cs;
-    return launch_attn_w4a16_rows(A, R, a->B, s);
+    return launch_attn_w4a16_rows(A, R, a->B, s, runs);
   };
   return a->n_rot > 0 && !a->cs ? with_rope_table(a->n_ctx, a->n_rot, s, launch) : launch((const double2 *)a->cs);
 }
+}  // namespace
+int vsim_op_attn_w4a16_rows(const vsim_attn_batch_args *a, void *stream) { return attn_w4a16_rows_op(a, stream, false); }
+int vsim_op_attn_w4a16_runs(const vsim_attn_batch_args *a, void *stream) { return attn_w4a16_rows_op(a, stream, true); }
 int vsim_op_attn_w4a16_prompt(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
                               float scale, float *out, void *scratch, size_t scratch_bytes, void *stream) {
   return launch_attn_w4a16_tile(Q, kc, vc, d, H, N, n_past, scale, out, (hipStream_t)stream, scratch, scratch_bytes);

@@ -163,7 +163,13 @@ struct AttnRows {
   size_t loff;                   // the layer's offset into a cache, in floats
   const int *npast;              // [B] device positions
 };
-int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s);
+int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s, bool runs = false);
+// Runs of rows (layer.hip, 3c): rows may share a cache when those that do sit at distinct positions.
+// launch_kv_rows (k_kv_rows) writes every row's new K (after RoPE) and V cache rows with the heads'
+// arithmetic; launch_attn_decode_runs is that launch and then k_attn_decode_runs, the heads without
+// their cache writes, each row over keys 0..npast[b] (launch_attn_decode_batch with runs = true).
+int launch_kv_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s);
+int launch_attn_decode_runs(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s);
 // exact-mode chain GEMV (gemv_chain.hip): a batch of jobs with the GemvBatch epilogues
 int launch_gemv_chain_batch(const GemvBatch &B, hipStream_t s);
 // true when launch_gemv_chain_batch runs B as k_gemv_solo (else k_gemv_chain32)
@@ -475,7 +481,10 @@ bool attn_w4a16_supported(int d, int E);  // d in {64, 96, 128, 256} and E % 64 
 int attn_w4a16_prepare();                 // the kernels' LDS attributes, once
 int launch_attn_w4a16_tile(const float *Q, const float *kc, const float *vc, int d, int H, int N, int n_past,
                            float scale, float *out, hipStream_t s, void *scratch, size_t scratch_bytes);
-int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s);
+int launch_attn_w4a16_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s, bool runs = false);
+// the single-query form for runs of rows: launch_kv_rows, then the form without its cache writes
+// (k_attn_w4a16_runs), K clamped and V zeroed past each row's own position as before
+int launch_attn_w4a16_runs(const AttnJob &A, const AttnRows &R, int B, hipStream_t s);
 // The heads' completion flags of the layer tail (r06): one 8-byte {unused, tag} sc1 granule per head
 // workgroup, tag = epoch << 8 | layer + 1 (the epoch advanced by the step's first k_ln_quant), so
 // no counter has to be zeroed between layers or steps

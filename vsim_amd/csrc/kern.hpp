@@ -53,6 +53,45 @@ __device__ __forceinline__ void quantize_block(const float *v, uint8_t *qs_out, 
   }
 }
 
+// ------------------------------------------------------------------ RoPE of the decode heads
+// The decode attention's RoPE step (ggml.c:6117-6152 rotate-half, style 0; 5952-5973 GPT-J pairs,
+// style 1) on one head's rows in LDS at position p: thread tid of nt takes the pairs j = tid,
+// tid + nt, .. < n_rot / 2 of the query row qh (Q) and of the new key's row kh (K).  Products in
+// double, one (float) rounding per element; n_rot = 0: nothing.  The one copy of these lines:
+// attn_body (attn.hpp), the fp16 form's rows (attn_w4a16.hip) and k_kv_rows (layer.hip) call it, so
+// a key rotated by k_kv_rows is the key the one-launch kernels write.
+template <bool Q, bool K>
+__device__ __forceinline__ void rope_head(float *qh, float *kh, const double2 *__restrict__ cs, int n_rot, int style,
+                                          int p, int tid, int nt) {
+  const int half = n_rot / 2;
+  for (int j = tid; j < half; j += nt) {
+    const double2 c = cs[(size_t)p * half + j];
+    const int i0 = style == 0 ? j : 2 * j, i1 = style == 0 ? j + half : 2 * j + 1;
+    double q0 = 0.0, q1 = 0.0, k0 = 0.0, k1 = 0.0;
+    if constexpr (Q) { q0 = qh[i0]; q1 = qh[i1]; }
+    if constexpr (K) { k0 = kh[i0]; k1 = kh[i1]; }
+    if (style == 0) {
+      if constexpr (Q) {
+        qh[i0] = (float)(c.x * q0 - c.y * q1);
+        qh[i1] = (float)(c.x * q1 + c.y * q0);
+      }
+      if constexpr (K) {
+        kh[i0] = (float)(c.x * k0 - c.y * k1);
+        kh[i1] = (float)(c.x * k1 + c.y * k0);
+      }
+    } else {
+      if constexpr (Q) {
+        qh[i0] = (float)(q0 * c.x - q1 * c.y);
+        qh[i1] = (float)(q0 * c.y + q1 * c.x);
+      }
+      if constexpr (K) {
+        kh[i0] = (float)(k0 * c.x - k1 * c.y);
+        kh[i1] = (float)(k0 * c.y + k1 * c.x);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ greedy key
 // A logit and its index as one 64-bit key whose unsigned order is numpy.argmax's: the value's
 // bits mapped to an unsigned order (NaN -> all ones, -0.0 -> +0.0) above ~index, so the largest

@@ -156,8 +156,8 @@ int launch_attn_decode(const AttnJob &A, int n_ctx, hipStream_t s) {
 // The batched decode step: workgroup (hs, b) is the same head of row b -- its own cache, its own
 // position, its own slices of Q / K / V and of the Q4 output rows -- so a row's bits are those of
 // k_attn_decode on that row alone, whatever shares the launch.
-__global__ void __launch_bounds__(ATT_THREADS) k_attn_decode_batch(AttnJob A, AttnRows R) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+template <bool KW>
+__device__ __forceinline__ void attn_batch_row(AttnJob &A, const AttnRows &R, float *sm) {
   const int b = blockIdx.y, E = A.d * A.H;
   const size_t ro = (size_t)b * E, bo = (size_t)b * (E / QK);
   A.q += ro;
@@ -170,10 +170,59 @@ __global__ void __launch_bounds__(ATT_THREADS) k_attn_decode_batch(AttnJob A, At
   A.oq_d += bo;
   A.oxd += ro;
   if (A.out) A.out += ro;
-  attn_body<ATT_THREADS>(A, blockIdx.x, sm);
+  attn_body<ATT_THREADS, false, KW>(A, blockIdx.x, sm);
 }
 
-int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s) {
+__global__ void __launch_bounds__(ATT_THREADS) k_attn_decode_batch(AttnJob A, AttnRows R) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  attn_batch_row<true>(A, R, sm);
+}
+
+// ------------------------------------------------------------------ 3c. attention, runs of rows
+// A run: consecutive tokens of one sequence as consecutive rows of the batch, row j at position
+// p + j of the same cache.  One launch cannot take them -- a head writes its row's K / V rows and
+// reads the cache in one workgroup, and nothing orders the workgroups of two rows -- so two do:
+// k_kv_rows writes every row's new K (after RoPE) and V rows, the kernel boundary orders them, and
+// k_attn_decode_runs (attn_body with KW = false) reads keys 0..p + j per row and writes nothing to the
+// caches.  Row j never sees the rows after it (they lie past its position), so its bits are those of
+// k_attn_decode_batch on that row alone after the j rows before it.
+//
+// k_kv_rows: workgroup (h, b) rotates head h of row b's key at the row's position (rope_head, the
+// heads' own lines) and stores the K and V rows; d <= 256.
+constexpr int KVR_THREADS = 128;
+__global__ void __launch_bounds__(KVR_THREADS) k_kv_rows(AttnJob A, AttnRows R) {
+  __shared__ float kh[256];
+  const int h = blockIdx.x, b = blockIdx.y, d = A.d, E = A.d * A.H, tid = threadIdx.x;
+  const float *k = A.k + (size_t)b * E + h * d, *v = A.v + (size_t)b * E + h * d;
+  const int p = R.npast[b];
+  float *kc = R.kc[b] + R.loff + (size_t)p * E + h * d, *vc = R.vc[b] + R.loff + (size_t)p * E + h * d;
+  for (int i = tid; i < d; i += KVR_THREADS) {
+    kh[i] = k[i];
+    vc[i] = v[i];
+  }
+  __syncthreads();
+  rope_head<false, true>(nullptr, kh, A.cs, A.n_rot, A.style, p, tid, KVR_THREADS);
+  __syncthreads();
+  for (int i = tid; i < d; i += KVR_THREADS) kc[i] = kh[i];
+}
+
+__global__ void __launch_bounds__(ATT_THREADS) k_attn_decode_runs(AttnJob A, AttnRows R) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  attn_batch_row<false>(A, R, sm);
+}
+
+int launch_kv_rows(const AttnJob &A, const AttnRows &R, int B, hipStream_t s) {
+  if (A.d < 1 || A.d > 256 || A.H < 1 || B < 1 || B > VSIM_BATCH_MAX || !R.kc || !R.vc || !R.npast || !A.k || !A.v ||
+      A.n_rot < 0 || A.n_rot > A.d || A.n_rot % 2 || (A.n_rot > 0 && !A.cs)) {
+    set_error("kv_rows: 1..32 rows with their caches and positions, k and v, head dim at most 256, n_rot even");
+    return VSIM_EINVAL;
+  }
+  hipLaunchKernelGGL(k_kv_rows, dim3(A.H, B), dim3(KVR_THREADS), 0, s, A, R);
+  VSIM_HIP(hipGetLastError());
+  return VSIM_OK;
+}
+
+int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s, bool runs) {
   const int S = A.nsplit > 1 ? A.nsplit : 1;
   if (A.d % 32 != 0 || A.d > 256 || A.n_ctx != n_ctx || A.d % S != 0 || (A.d / S) % QK != 0) {
     set_error("attention: head dim must be a multiple of 32, at most 256");
@@ -184,9 +233,18 @@ int launch_attn_decode_batch(const AttnJob &A, const AttnRows &R, int B, int n_c
     return VSIM_EINVAL;
   }
   const size_t smem = (size_t)attn_lds_floats(A.d, n_ctx) * sizeof(float);
-  hipLaunchKernelGGL(k_attn_decode_batch, dim3(A.H * S, B), dim3(ATT_THREADS), smem, s, A, R);
+  if (runs) {
+    if (int rc = launch_kv_rows(A, R, B, s)) return rc;
+    hipLaunchKernelGGL(k_attn_decode_runs, dim3(A.H * S, B), dim3(ATT_THREADS), smem, s, A, R);
+  } else {
+    hipLaunchKernelGGL(k_attn_decode_batch, dim3(A.H * S, B), dim3(ATT_THREADS), smem, s, A, R);
+  }
   VSIM_HIP(hipGetLastError());
   return VSIM_OK;
+}
+
+int launch_attn_decode_runs(const AttnJob &A, const AttnRows &R, int B, int n_ctx, hipStream_t s) {
+  return launch_attn_decode_batch(A, R, B, n_ctx, s, true);
 }
 
 }  // namespace vsim

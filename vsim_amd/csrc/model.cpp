@@ -685,6 +685,9 @@ struct BatchDesc {
   // exact, decode_batch_fast fast, whatever the model's mode)
   int mode = VSIM_MODE_EXACT;
   const char *who = "";  // prefixes the error messages
+  // a rows batch of vsim_model_decode_runs: rows may share a cache (at distinct positions), so the
+  // attention is k_kv_rows + the heads without their cache writes instead of the one launch
+  bool runs = false;
 };
 
 // A batch on its way through the layers and the head, counting its launches into nk.  What
@@ -831,10 +834,17 @@ int run_layer(PromptBatch &B, int il) {
     AttnJob A = attn_job(decode_attn_desc(m, tab, ActRow{q4_rows(m->xq2, E, N), m->xd2}, 1), nullptr, nullptr, nullptr);
     if (w4a16) A.out = m->attn_in;  // the out-projection's operand is made from the f32 row
     const AttnRows R{D.rows->kc, D.rows->vc, loff, D.rows->npast};
-    if (wattn)
+    if (D.runs) {
+      if (wattn)
+        LAUNCH(m, nk, launch_attn_w4a16_runs(A, R, N, s), "k_kv_rows + k_attn_w4a16_runs", 0.0);
+      else
+        LAUNCH(m, nk, launch_attn_decode_runs(A, R, N, m->n_ctx, s), "k_kv_rows + k_attn_decode_runs", 0.0);
+      ++nk;  // (two launches)
+    } else if (wattn) {
       LAUNCH(m, nk, launch_attn_w4a16_rows(A, R, N, s), "k_attn_w4a16_rows", 0.0);
-    else
+    } else {
       LAUNCH(m, nk, launch_attn_decode_batch(A, R, N, m->n_ctx, s), "k_attn_decode_batch", 0.0);
+    }
   } else if (!rope_epi) {
     RC(launch_rope_kv_write(G.rotary == ROT_GPTJ ? 1 : 0, m->Qb, m->Kb, m->Vb, kc, vc, d, H, N, n_past,
                             G.rotary == ROT_NONE ? 0 : m->hp.n_rot, m->rope_cs, s));
@@ -2352,6 +2362,9 @@ namespace {
 // exact mode; vsim_model_decode_batch_fast: fast, vsim_model_decode_batch_w4a16: weight-only, whatever
 // the model's mode)
 // -- or, with samplers, the sampled step (vsim_model_decode_batch_sample): next[b] drawn by samplers[b]
+int decode_rows_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
+                     float *logits, int32_t *next, vsim_sampler *const *samplers, bool runs);
+
 int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past,
                       const int32_t *tokens, float *logits, int32_t *next, vsim_sampler *const *samplers = nullptr) {
   if (!m || !seq || !n_past || !tokens) { set_error("decode_batch: null argument"); return VSIM_EINVAL; }
@@ -2372,6 +2385,14 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
     if (n_past[b] < 0 || n_past[b] >= m->n_ctx) { set_error("decode_batch: n_past outside [0, n_ctx)"); return VSIM_EINVAL; }
     if (tokens[b] < 0 || tokens[b] >= V) { set_error("decode_batch: token id out of range"); return VSIM_EINVAL; }
   }
+  return decode_rows_impl(m, mode, B, seq, n_past, tokens, logits, next, samplers, false);
+}
+
+// The checked step: row b on slot seq[b] at n_past[b].  runs: the rows of vsim_model_decode_runs,
+// where consecutive rows may name one slot at consecutive positions.
+int decode_rows_impl(vsim_model *m, int mode, int B, const int32_t *seq, const int32_t *n_past, const int32_t *tokens,
+                     float *logits, int32_t *next, vsim_sampler *const *samplers, bool runs) {
+  const int V = m->hp.n_vocab;
   // the sampled step: which rows' candidates the device makes (the others: sample_host on the row's logits)
   bool on_dev[VSIM_BATCH_MAX] = {};
   bool any_dev = false;
@@ -2400,7 +2421,8 @@ int decode_batch_impl(vsim_model *m, int mode, int B, const int32_t *seq, const 
   const BatchKind kind = mode == VSIM_MODE_EXACT  ? BatchKind::ROWS_EXACT
                          : mode == VSIM_MODE_FAST ? BatchKind::ROWS_FAST
                                                   : BatchKind::ROWS_W4A16;
-  const BatchDesc D{.kind = kind, .N = B, .rows = m->bw_dev, .mode = mode, .who = "decode_batch"};
+  const BatchDesc D{.kind = kind, .N = B, .rows = m->bw_dev, .mode = mode, .who = runs ? "decode_runs" : "decode_batch",
+                    .runs = runs};
   RC(enqueue_prompt(m, D, tokens, nullptr, nk));
   RC(run_head(m, D, m->inpL, m->score_x, "lm_head (batch)", nk));
   int32_t *am_dev = (int32_t *)m->score_out;
@@ -2469,6 +2491,42 @@ int vsim_model_decode_batch_sample_w4a16(vsim_model *m, int B, const int32_t *se
                                          const int32_t *tokens, vsim_sampler *const *samplers, int32_t *next) {
   if (!samplers || !next) { set_error("decode_batch_sample: null argument"); return VSIM_EINVAL; }
   return decode_batch_impl(m, VSIM_MODE_W4A16, B, seq, n_past, tokens, nullptr, next, samplers);
+}
+
+int vsim_model_decode_runs(vsim_model *m, int mode, int S, const int32_t *seq, const int32_t *n_past,
+                           const int32_t *len, const int32_t *tokens, float *logits, int32_t *next) {
+  if (!m || !seq || !n_past || !len || !tokens) { set_error("decode_runs: null argument"); return VSIM_EINVAL; }
+  if (!m->first || !m->last) { set_error("decode_runs: needs a whole model"); return VSIM_EINVAL; }
+  if (mode != VSIM_MODE_EXACT && mode != VSIM_MODE_FAST && mode != VSIM_MODE_W4A16) {
+    set_error("decode_runs: mode must be VSIM_MODE_EXACT, VSIM_MODE_FAST or VSIM_MODE_W4A16");
+    return VSIM_EINVAL;
+  }
+  if (mode == VSIM_MODE_EXACT && m->mode != VSIM_MODE_EXACT) {
+    set_error("decode_runs: exact products on a model in exact mode only");
+    return VSIM_EINVAL;
+  }
+  if (S < 1) { set_error("decode_runs: S < 1"); return VSIM_EINVAL; }
+  const int V = m->hp.n_vocab, nslot = 1 + (int)m->kslot.size();
+  // the rows of the batch: run s as len[s] rows of slot seq[s] at n_past[s], n_past[s] + 1, ..
+  int32_t row_seq[VSIM_BATCH_MAX], row_npast[VSIM_BATCH_MAX];
+  int N = 0;
+  for (int s = 0; s < S; ++s) {
+    if (len[s] < 1) { set_error("decode_runs: a run needs at least one token"); return VSIM_EINVAL; }
+    if (len[s] > VSIM_BATCH_MAX - N) { set_error("decode_runs: more than 32 rows in all"); return VSIM_EINVAL; }
+    if (seq[s] < 0 || seq[s] >= nslot) { set_error("decode_runs: slot outside the reserve (seq_reserve)"); return VSIM_EINVAL; }
+    for (int a = 0; a < s; ++a)
+      if (seq[a] == seq[s]) { set_error("decode_runs: a slot is named twice (one run per slot)"); return VSIM_EINVAL; }
+    if (n_past[s] < 0 || n_past[s] > m->n_ctx - len[s]) {
+      set_error("decode_runs: a run outside [0, n_ctx)");
+      return VSIM_EINVAL;
+    }
+    for (int j = 0; j < len[s]; ++j, ++N) {
+      if (tokens[N] < 0 || tokens[N] >= V) { set_error("decode_runs: token id out of range"); return VSIM_EINVAL; }
+      row_seq[N] = seq[s];
+      row_npast[N] = n_past[s] + j;
+    }
+  }
+  return decode_rows_impl(m, mode, N, row_seq, row_npast, tokens, logits, next, nullptr, true);
 }
 
 int vsim_model_seq_copy(vsim_model *m, int dst, int src, int n_tokens) {

@@ -66,6 +66,7 @@ EXPORTS = [
     "vsim_w4a16_set_attn", "vsim_op_attn_w4a16_prompt", "vsim_op_attn_w4a16_rows",
     "vsim_op_gemm_q4_f16x", "vsim_op_rope_kv_write", "vsim_op_add_residual", "vsim_op_add_rows",
     "vsim_op_gelu_bias", "vsim_op_attn_softmax_alibi", "vsim_op_alibi_slopes", "vsim_op_kqv_causal_merged",
+    "vsim_op_attn_decode_runs", "vsim_op_attn_w4a16_runs", "vsim_model_decode_runs",
 ]
 
 BATCH_MAX = 32  # VSIM_BATCH_MAX
@@ -379,6 +380,9 @@ def lib():
     L.vsim_w4a16_set_attn.argtypes = [ci]
     L.vsim_op_attn_w4a16_prompt.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp, sz, vp]
     L.vsim_op_attn_w4a16_rows.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
+    L.vsim_op_attn_decode_runs.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
+    L.vsim_op_attn_w4a16_runs.argtypes = [ctypes.POINTER(AttnBatchArgs), vp]
+    L.vsim_model_decode_runs.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
     L.vsim_op_gemv_batch.argtypes = [ctypes.POINTER(GemvBatchArgs), i32p, vp]
     L.vsim_op_gemm_q4_f16x.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.vsim_op_rope_kv_write.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
@@ -650,6 +654,14 @@ def attn_w4a16_rows(q, k, v, kc, vc, n_past, cs, B, d, H, n_rot, style, n_ctx, s
     check(lib().vsim_op_attn_w4a16_rows(ctypes.byref(a), stream), "attn_w4a16_rows")
 
 
+def attn_w4a16_runs(q, k, v, kc, vc, n_past, cs, B, d, H, n_rot, style, n_ctx, scale, out, stream=None):
+    """vsim_op_attn_w4a16_runs: attn_w4a16_rows' arguments for rows that may share a cache at distinct
+    positions (runs of consecutive tokens): k_kv_rows, then the form without its cache writes."""
+    a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), None, B, d, H, n_rot,
+                      style, n_ctx, 0, float(scale), ptr(out), None, None)
+    check(lib().vsim_op_attn_w4a16_runs(ctypes.byref(a), stream), "attn_w4a16_runs")
+
+
 def batch_set_fast_gemm(enable) -> int:
     """How q4_gemm_fast_rows and Model.decode_batch_fast run their products: 0 one k_gemv_fast
     launch per row, 1 (default) k_gemm_fast_rows from the row count on at which it was measured
@@ -664,6 +676,16 @@ def attn_decode_batch(q, k, v, kc, vc, n_past, cs, alibi, B, d, H, n_rot, style,
     a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), B, d, H, n_rot,
                       style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
     check(lib().vsim_op_attn_decode_batch(ctypes.byref(a), stream), "attn_decode_batch")
+
+
+def attn_decode_runs(q, k, v, kc, vc, n_past, cs, alibi, B, d, H, n_rot, style, n_ctx, kqv_nth, scale, out, oq, oxd,
+                     stream=None):
+    """vsim_op_attn_decode_runs: attn_decode_batch's arguments for rows that may share a cache at
+    distinct positions (runs of consecutive tokens): k_kv_rows, then the heads without their cache
+    writes.  Row j of a run gets the bits of attn_decode_batch on it alone after the rows before it."""
+    a = AttnBatchArgs(ptr(q), ptr(k), ptr(v), ptr(kc), ptr(vc), ptr(n_past), ptr(cs), ptr(alibi), B, d, H, n_rot,
+                      style, n_ctx, kqv_nth, float(scale), ptr(out), ptr(oq), ptr(oxd))
+    check(lib().vsim_op_attn_decode_runs(ctypes.byref(a), stream), "attn_decode_runs")
 
 
 def tail_attn(q, k, v, kc, vc, n_past, cs, alibi, d, H, n_rot, style, n_ctx, kqv_nth, scale, out, oq, oxd, nsplit,
@@ -877,6 +899,27 @@ class Model:
         nxt = np.zeros(max(B, 1), np.int32)
         check(fn(self.h, B, ptr(sq), ptr(npst), ptr(tok), ptr(lg), ptr(nxt)), who)
         return lg, nxt[:B]
+
+    def decode_runs(self, seqs, n_past, runs, mode, want_logits=True):
+        """vsim_model_decode_runs: one batched step in which slot seqs[s] takes the token list runs[s]
+        at positions n_past[s], n_past[s] + 1, ..; mode (MODE_EXACT, MODE_FAST or MODE_W4A16) names the
+        products.  Every row is bit for bit the one-row decode_batch* step of that mode on the slot
+        after the rows before it.  Returns (logits [N][n_vocab] in run order or None, [next ids of
+        each run as an int32 array])."""
+        sq = np.ascontiguousarray(seqs, np.int32)
+        npst = np.ascontiguousarray(n_past, np.int32)
+        runs = [np.ascontiguousarray(r, np.int32).reshape(-1) for r in runs]
+        if not (sq.size == npst.size == len(runs)):
+            raise ValueError("decode_runs: one slot, position and run per sequence")
+        ln = np.ascontiguousarray([r.size for r in runs], np.int32)
+        tok = np.ascontiguousarray(np.concatenate(runs) if runs else [], np.int32)
+        N = int(tok.size)
+        lg = np.zeros((N, self.n_vocab), np.float32) if want_logits else None
+        nxt = np.zeros(max(N, 1), np.int32)
+        check(lib().vsim_model_decode_runs(self.h, int(mode), int(sq.size), ptr(sq), ptr(npst), ptr(ln), ptr(tok),
+                                           ptr(lg), ptr(nxt)), "decode_runs")
+        ends = np.cumsum(ln)
+        return lg, [nxt[e - l:e] for e, l in zip(ends, ln)]
 
     def decode_batch_sample(self, seqs, n_past, tokens, samplers, fast=False, mode=None):
         """One sampled decode step for len(seqs) sequences: decode_batch (or decode_batch_fast), then
